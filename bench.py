@@ -13,7 +13,13 @@ Default workload (N=1..8, strong scaling): C3* — 1M series x 3600 points
 over the ranks by contiguous span ranges. `--config c2` runs configs[1]
 (10k float series x 1 day @10s, avg + 1m-avg).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3s|c2|c1]
+A plain run sets up, warms up, times the K steps and prints the line. `--full`
+adds the measurements that take runs of their own (the CPU baseline of the
+oracle on the host cores, the achievable-bandwidth probes). `--dump-outputs
+DIR` writes what the last timed step returned as DIR/<name>.npy; the inputs
+are seeded, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3s|c2|c1] [--full] [--dump-outputs DIR]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 """
 import argparse
@@ -298,6 +304,48 @@ def cpu_baseline_c5(batch, seconds=10.0):
 
 _JSON_OUT = None
 
+# --dump-outputs: at most this many bytes of .npy payload in all
+DUMP_BUDGET = 64 * 1000 * 1000
+
+
+def sample_index(n, cap, seed):
+    """None when n <= cap, else a fixed (seeded, sorted) sample of cap indices
+    of range(n): the same indices in every run with the same arguments."""
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def take(a, idx):
+    return a if idx is None else a[idx]
+
+
+def point_arrays(ts, isi, bits, idx=None):
+    """The (timestamp, is_int, value bits) points of a result as float arrays:
+    `value` is the long or double each point holds, and value_bits_hi32 /
+    value_bits_lo32 are the halves of its 64 bits, so two builds can also be
+    compared bit for bit (a float64 holds a uint32 exactly)."""
+    ts, isi, bits = take(ts, idx), take(isi, idx), take(bits, idx)
+    u = bits.view(np.uint64)
+    return {"ts": ts.astype(np.float64), "is_int": isi.astype(np.float32),
+            "value": np.where(isi != 0, bits.astype(np.float64), bits.view(np.float64)),
+            "value_bits_hi32": (u >> np.uint64(32)).astype(np.float64),
+            "value_bits_lo32": (u & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one <name>.npy per array, float32 / float64 only."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: {a.dtype}")
+        total += a.nbytes
+        if total > DUMP_BUDGET:
+            raise ValueError(f"--dump-outputs: more than {DUMP_BUDGET} bytes at {name}")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
 
 def set_options(ctx, opts):
     for o in opts:
@@ -380,6 +428,27 @@ def bench_c5(args):
     st = o["st"].cpu().numpy()
     ql = o["ql"].cpu().numpy().astype(np.int64)
     vl = o["vl"].cpu().numpy().astype(np.int64)
+    if args.dump_outputs:
+        # what a caller of tsdbhip_compact_rows receives from the last timed
+        # call: the per-row results (a seeded sample of 1M rows of a larger
+        # batch) and the compacted qualifier / value bytes of a seeded sample
+        # of rows, concatenated in row order (the gaps between rows are
+        # undefined)
+        ri = sample_index(R, 1_000_000, 11)
+        f32, f64 = (lambda a: take(a, ri).astype(np.float32)), (lambda a: take(a, ri).astype(np.float64))
+        qo, vo = o["qo"].cpu().numpy(), o["vo"].cpu().numpy()
+        bi = sample_index(R, 8192, 12)
+        bi = np.arange(R) if bi is None else bi
+        packed = compaction.RowsResult._packed
+        qb = packed(o["q"].cpu().numpy(), qo[bi], ql[bi])
+        vb = packed(o["v"].cpu().numpy(), vo[bi], vl[bi])
+        dump_outputs(args.dump_outputs, {
+            "row_status": f32(st), "row_qual_len": f32(ql), "row_val_len": f32(vl),
+            "row_qual_off": f64(qo), "row_val_off": f64(vo), "row_write": f32(o["w"].cpu().numpy()),
+            "row_keep_kv": f32(o["k"].cpu().numpy()),
+            "qual_bytes_of_sampled_rows": take(qb, sample_index(len(qb), 2_000_000, 13)).astype(np.float32),
+            "val_bytes_of_sampled_rows": take(vb, sample_index(len(vb), 2_000_000, 14)).astype(np.float32),
+            "counts": np.array([R, int(out.n_complex)], np.float64)})
     # input cell bytes + output compacted bytes
     row_q = np.diff(b.row_qual_off.astype(np.int64))
     row_v = np.diff(b.row_val_off.astype(np.int64))
@@ -425,7 +494,7 @@ def bench_c5(args):
             res["h2d"] = h2d_leg_c5(ctx, L, b)
         except Exception as e:  # diagnostics only; never costs the line
             res["h2d"] = {"error": repr(e)}
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline_c5(b, args.cpu_seconds)
     emit(res)
     ctx.close()
@@ -604,7 +673,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3s", choices=sorted(CONFIGS))
     ap.add_argument("--series", type=int, default=0, help="override the number of series")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the line's own figures, the measurements that take runs of their own: the CPU "
+                         "baseline (the oracle on the host cores) and the achievable-bandwidth probes "
+                         "(roofline.achievable_GBs, frac_of_read_stream)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed call returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed seeded sample of a larger result)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--exact", action="store_true", help="TSDBHIP_EXACT_ORDER")
     ap.add_argument("--groups", type=int, default=0, help="GROUP BY: split the series into this many SpanGroups "
@@ -624,6 +700,8 @@ def main():
                     help="harness check without a GPU: the multi-rank timing/barrier/report path with a "
                          "no-op step (its value is meaningless and says so)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
         # one process per GPU: start the N ranks under torch.distributed.run
@@ -777,11 +855,29 @@ def main():
     hot_ms, total_ms, red_ms = [tsum.hot_ms / ncalls], [tsum.total_ms / ncalls], [tsum.reduce_ms / ncalls]
     emitted = [int(tsum.n_emitted) // ncalls, int(tsum.n_grid) // ncalls]
     hot_kernel = tsum.hot_kernel
+    if args.dump_outputs and rank == 0:
+        # the points the last timed call returned (rank 0's buffers: the whole
+        # group's when series-sharded, this rank's groups under GROUP BY, all
+        # groups' points concatenated in group order); a seeded sample of
+        # 1.5M points of a larger result
+        if G > 1:
+            n_out = [int(outs[g].n_out) for g in range(Gl)]
+            sel = np.concatenate([np.arange(g * gcap, g * gcap + n_out[g]) for g in range(Gl)])
+            pts = (g_ts[sel], g_isi[sel], g_bits[sel])
+            counts = {"counts": np.array([Gl, sum(int(outs[g].n_input_points) for g in range(Gl))], np.float64),
+                      "group_n_out": np.array(n_out, np.float64)}
+        else:
+            n_out = int(out.n_out)
+            pts = (ts[:n_out], isi[:n_out], bits[:n_out])
+            counts = {"counts": np.array([n_out, int(out.n_input_points)], np.float64)}
+        dump_outputs(args.dump_outputs, dict(point_arrays(*pts, sample_index(len(pts[0]), 1_500_000, 11)),
+                                             **counts))
     # achievable bandwidth on this box, same buffers (tsdbhip_bw_probe): a
-    # streaming read with the downsampler's geometry and a D2D copy
+    # streaming read with the downsampler's geometry and a D2D copy (--full:
+    # runs of their own)
     probe = {}
     width = 4 if kind == _abi.SYN_FLOAT32 else 8
-    for mode, name in (((0, "read_stream"), (1, "d2d_copy")) if cfg["gen"] == "device" else ()):
+    for mode, name in (((0, "read_stream"), (1, "d2d_copy")) if args.full and cfg["gen"] == "device" else ()):
         ms, nb = C.c_float(), C.c_uint64()
         best = None
         for _ in range(3):
@@ -910,7 +1006,7 @@ def main():
                 res["h2d"] = h2d_leg(ctx, L, cfg, min(n_series, 100_000))
             except Exception as e:  # diagnostics only; never costs the line
                 res["h2d"] = {"error": repr(e)}
-        if not args.no_cpu and world == 1 and not rehearse:
+        if args.full and not args.no_cpu and world == 1 and not rehearse:
             res["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds)
         emit(res)
     if cfg["gen"] == "device":

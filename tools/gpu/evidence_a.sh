@@ -10,11 +10,11 @@ timeout -k 10 900 python -u -m pytest tests -q -x --tb=short -rf --timeout 600 -
   > $O/pytest_gpu.log 2>&1; rc=$?; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1
 cat $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 600 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 cut -c1-300 $O/bench_default.json
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/benchprof -o run -f csv -- \
-  python3 bench.py > $O/bench_under_rocprof.json 2> $O/benchprof.err || exit 1
+  python3 bench.py --full > $O/bench_under_rocprof.json 2> $O/benchprof.err || exit 1
 for n in 2 4 8; do
   timeout -k 10 300 python -u bench.py --no-cpu --steps 20 --warmup 3 --rehearse-shards $n > $O/rehearse_$n.json 2>$O/rehearse_$n.err || exit 1
   cut -c1-160 $O/rehearse_$n.json
