@@ -21,6 +21,13 @@
  *   tsdbhip_spangroup_run_batch — the SpanGroup[] of a GROUP BY query
  *       (TsdbQuery.groupByAndAggregate, TsdbQuery.java:294-363), all groups in
  *       one call.
+ *   tsdbhip_groupby_plan — the grouping loop of TsdbQuery.groupByAndAggregate
+ *       itself (TsdbQuery.java:310-348: Tags.getValueId per GROUP BY tag,
+ *       Tags.java:213-227, the ByteMap of group keys, the dropped spans of
+ *       :339-344) and SpanGroup.getTags / getAggregatedTags of every group
+ *       (computeTags, SpanGroup.java:149-191), from the spans' row keys.
+ *   tsdbhip_desc_gather — the repacking of the spans' rows into the plan's
+ *       batch order for a descriptor already in HBM.
  *   tsdbhip_format_points  — the text GraphHandler.respondAsciiQuery,
  *       Plot.dumpToFiles and CliQuery print for each DataPoint.
  *   tsdbhip_compact_rows   — CompactionQueue.compact(row, compacted[])
@@ -49,7 +56,7 @@
 extern "C" {
 #endif
 
-#define TSDBHIP_ABI_VERSION 7
+#define TSDBHIP_ABI_VERSION 8
 
 /* ---- return codes ---------------------------------------------------- */
 #define TSDBHIP_OK               0
@@ -88,6 +95,8 @@ extern "C" {
 #define TSDBHIP_HOT_UG_DEV      8 /* k_ug_dev: integer dev chains of a uniform group */
 #define TSDBHIP_HOT_DS_E        9 /* k_ds_reg in the uniform E variant: the spans' bucket values
                                      on the key's buckets (k_ug_reduce runs after it) */
+#define TSDBHIP_HOT_GROUPBY    10 /* k_gb_count + scan + k_gb_scatter: the radix sort passes of
+                                     tsdbhip_groupby_plan */
 #define TSDBHIP_HOT_COMPACT     4 /* k_compact_wave: every row's classification and compaction
                                      in one pass (tsdbhip_compact_rows)      */
 
@@ -372,6 +381,95 @@ int tsdbhip_timing_totals(tsdbhip_ctx* ctx, tsdbhip_timing* sum, uint64_t* n_cal
  */
 int tsdbhip_spangroup_run_batch(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* desc, uint32_t n_groups,
                                 const uint32_t* group_span_start, tsdbhip_sg_out* outs);
+
+/* ---- GROUP BY planning and SpanGroup tags (ABI v8) ---------------------- */
+/*
+ * tsdbhip_groupby_plan: the grouping of TsdbQuery.groupByAndAggregate
+ * (TsdbQuery.java:294-363) and computeTags (SpanGroup.java:149-173) of every
+ * group, from the spans' row keys.
+ *
+ * Input: the row keys of the spans in findSpans' TreeMap order, i.e. strictly
+ * increasing under SpanCmp (TsdbQuery.java:594-621: metric bytes, then
+ * everything after the 4 base-time bytes, unsigned, the shorter key first on
+ * a common prefix). Two adjacent keys that are equal under SpanCmp (also: that
+ * differ only in base time) or out of order: TSDBHIP_E_UNSORTED, the message
+ * names the first offending span. A key shorter than metric_width + 4, whose
+ * tag part is no multiple of name_width + value_width or holds more than
+ * TSDBHIP_MAX_TAGS pairs, a key_off that decreases or does not end at
+ * key_nbytes, group_bys not strictly ascending, a width outside 1..8 or
+ * n_group_bys > TSDBHIP_MAX_TAGS: TSDBHIP_E_INVALID_ARG. Tag names inside a
+ * key need not be sorted: the lookup is Tags.getValueId's linear scan, the
+ * first match wins.
+ *
+ * Output: groups in ByteMap order (unsigned lexicographic) of their keys, a
+ * group's key being the value ids of the group_bys tags in group_bys order;
+ * the spans of a group in input order. A span lacking a group_bys tag is
+ * dropped (TsdbQuery.java:339-344) and counted. n_group_bys == 0: one group of
+ * every span, key of length 0 (TsdbQuery.java:298-309). n_spans == 0: no
+ * group. A group exists even when span_kept clears all its spans (the
+ * reference constructs the SpanGroup before SpanGroup.add filters); its
+ * group_ntags is 0.
+ *
+ * Tags: group_tags holds the (name value) pairs of the group's first kept
+ * span in key order; bit i of group_common is set iff every other kept span
+ * of the group has pair i's name with pair i's value: SpanGroup.getTags() is
+ * the pairs whose bit is set, getAggregatedTags() the names of the others (in
+ * key order; the reference's HashSet has no defined order). A name only later
+ * spans carry is reported nowhere, as in the reference. A key that repeats a
+ * tag name: unspecified.
+ *
+ * n_groups > group_capacity: TSDBHIP_E_CAPACITY with n_groups, n_grouped and
+ * n_dropped set and no array written. tsdbhip_last_timing: total_ms, hot_ms
+ * (the sort passes), hot_kernel = TSDBHIP_HOT_GROUPBY, n_grid = the number of
+ * sort passes run, alg_bytes = key bytes read + output bytes written. A
+ * multi-device context runs the call on its first device.
+ */
+#define TSDBHIP_MAX_TAGS 8            /* Const.MAX_NUM_TAGS */
+
+typedef struct tsdbhip_keys_desc {
+  uint32_t flags;            /* TSDBHIP_DESC_DEVICE: key_off, key_bytes, span_kept are device pointers */
+  uint32_t n_spans;
+  uint8_t  metric_width, name_width, value_width;   /* each 1..8 (UniqueId widths) */
+  uint8_t  n_group_bys;      /* 0..TSDBHIP_MAX_TAGS; 0 = no GROUP BY (TsdbQuery.java:298-309) */
+  uint32_t reserved0;
+  const uint64_t* key_off;   /* [n_spans+1]; span s's row key is key_bytes[key_off[s], key_off[s+1]) */
+  const uint8_t*  key_bytes; /* full row keys: metric | base_time(4) | (name value)*; base time ignored */
+  uint64_t        key_nbytes;
+  const uint8_t*  span_kept; /* [n_spans] or NULL (all kept): SpanGroup.add's time filter, by the caller */
+  const uint8_t*  group_bys; /* HOST always: n_group_bys * name_width bytes, strictly ascending (unsigned) */
+} tsdbhip_keys_desc;
+
+typedef struct tsdbhip_groups_out {   /* every array is a HOST array owned by the caller */
+  uint32_t  group_capacity;  /* in */
+  uint32_t  n_groups;        /* out; also set on TSDBHIP_E_CAPACITY so the caller can retry */
+  uint32_t  n_grouped;       /* out: spans placed in some group */
+  uint32_t  n_dropped;       /* out: spans lacking a group_by tag (TsdbQuery.java:339-344) */
+  uint32_t* order;           /* [n_spans]: span indices in batch order, first n_grouped valid */
+  uint32_t* group_span_start;/* [group_capacity+1]: exactly what tsdbhip_spangroup_run_batch takes */
+  uint8_t*  group_key;       /* [group_capacity * n_group_bys*value_width] the ByteMap keys */
+  uint8_t*  group_ntags;     /* [group_capacity] tag count of the group's first kept span; 0 if none kept */
+  uint8_t*  group_tags;      /* [group_capacity * TSDBHIP_MAX_TAGS*(name_width+value_width)] that span's pairs */
+  uint8_t*  group_common;    /* [group_capacity] bit i set: pair i is in every kept span of the group */
+} tsdbhip_groups_out;
+
+int tsdbhip_groupby_plan(tsdbhip_ctx* ctx, const tsdbhip_keys_desc* keys, tsdbhip_groups_out* out);
+
+/*
+ * The spans order[0..n) of the device-resident descriptor `in`
+ * (TSDBHIP_DESC_DEVICE, else TSDBHIP_E_INVALID_ARG: a host descriptor is
+ * repacked by its packer) as a descriptor of their own, in that order: the
+ * batch order tsdbhip_groupby_plan returns. `out` receives the query fields
+ * and flags of `in`, n_spans = n, n_rows = the gathered row count;
+ * span_row_start and the five row_* arrays are new device arrays owned by
+ * ctx (tsdbhip_desc_gather_free releases them and zeroes the pointers; a
+ * second call is harmless). qual_bytes / val_bytes are BORROWED from `in`
+ * (a row's offsets stay valid; they no longer grow with the row index): `in`
+ * must outlive `out`. order is a host array; order[i] >= in->n_spans:
+ * TSDBHIP_E_INVALID_ARG. Not with TSDBHIP_SHARDED.
+ */
+int tsdbhip_desc_gather(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* in, const uint32_t* order,
+                        uint32_t n, tsdbhip_sg_desc* out);
+int tsdbhip_desc_gather_free(tsdbhip_ctx* ctx, tsdbhip_sg_desc* out);
 
 /* ---- output formatting (host cores, no GPU) ----------------------------- */
 /*

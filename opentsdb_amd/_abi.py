@@ -6,7 +6,7 @@ and the test harness.
 """
 import ctypes as C
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 PATH_ALIGNED_GROUP = 1  # tsdbhip_timing.paths (include/tsdbhip.h)
 PATH_ALIGNED_RERUN = 2
 PATH_LOCKSTEP = 4  # k_lockstep: one pass over the qualifiers and values of a lockstep group
@@ -95,7 +95,10 @@ class SgOut(C.Structure):
 
 HOT_NONE, HOT_DS_CHUNKS, HOT_DECODE_FAST, HOT_DECODE_GEN = 0, 1, 2, 3
 HOT_NAMES = {1: "k_ds_reg+k_ds_spans", 2: "k_decode_fast", 3: "k_decode_general", 4: "k_compact_wave",
-             5: "k_reduce", 6: "k_lockstep", 7: "k_ug_ds_reg", 8: "k_ug_dev", 9: "k_ds_reg"}
+             5: "k_reduce", 6: "k_lockstep", 7: "k_ug_ds_reg", 8: "k_ug_dev", 9: "k_ds_reg",
+             10: "k_gb_count+scan+k_gb_scatter"}
+HOT_GROUPBY = 10
+MAX_TAGS = 8  # TSDBHIP_MAX_TAGS (Const.MAX_NUM_TAGS)
 
 
 class Timing(C.Structure):
@@ -165,6 +168,40 @@ class SynthParams(C.Structure):
         ("step", C.c_uint32),
         ("kind", C.c_uint32),
         ("span0", C.c_uint32),
+    ]
+
+
+class KeysDesc(C.Structure):
+    """tsdbhip_keys_desc: the spans' row keys for tsdbhip_groupby_plan"""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("n_spans", C.c_uint32),
+        ("metric_width", C.c_uint8),
+        ("name_width", C.c_uint8),
+        ("value_width", C.c_uint8),
+        ("n_group_bys", C.c_uint8),
+        ("reserved0", C.c_uint32),
+        ("key_off", P64),
+        ("key_bytes", P8),
+        ("key_nbytes", C.c_uint64),
+        ("span_kept", P8),
+        ("group_bys", P8),
+    ]
+
+
+class GroupsOut(C.Structure):
+    """tsdbhip_groups_out: the plan (host arrays owned by the caller)"""
+    _fields_ = [
+        ("group_capacity", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_grouped", C.c_uint32),
+        ("n_dropped", C.c_uint32),
+        ("order", P32),
+        ("group_span_start", P32),
+        ("group_key", P8),
+        ("group_ntags", P8),
+        ("group_tags", P8),
+        ("group_common", P8),
     ]
 
 

@@ -25,6 +25,7 @@ EXPORTS = [
     "tsdbhip_desc_download", "tsdbhip_bw_probe", "tsdbhip_spangroup_run_batch",
     "tsdbhip_format_points", "tsdbhip_open_devices", "tsdbhip_open_mask", "tsdbhip_ranks",
     "tsdbhip_timing_totals", "tsdbhip_set_option",
+    "tsdbhip_groupby_plan", "tsdbhip_desc_gather", "tsdbhip_desc_gather_free",
 ]
 
 
@@ -91,6 +92,12 @@ def lib():
     L.tsdbhip_bw_probe.argtypes = [C.c_void_p, P(_abi.SgDesc), C.c_int32, C.c_uint32, P(C.c_float),
                                    P(C.c_uint64)]
     L.tsdbhip_bw_probe.restype = C.c_int
+    L.tsdbhip_groupby_plan.argtypes = [C.c_void_p, P(_abi.KeysDesc), P(_abi.GroupsOut)]
+    L.tsdbhip_groupby_plan.restype = C.c_int
+    L.tsdbhip_desc_gather.argtypes = [C.c_void_p, P(_abi.SgDesc), P(C.c_uint32), C.c_uint32, P(_abi.SgDesc)]
+    L.tsdbhip_desc_gather.restype = C.c_int
+    L.tsdbhip_desc_gather_free.argtypes = [C.c_void_p, P(_abi.SgDesc)]
+    L.tsdbhip_desc_gather_free.restype = C.c_int
     if L.tsdbhip_abi_version() != _abi.ABI_VERSION:
         raise TsdbHipError(_abi.E_INVALID_ARG, "ABI version mismatch")
     _LIB = L

@@ -12,6 +12,11 @@ Mirrors (names, argument meaning, error behaviour):
   group_by_and_aggregate          TsdbQuery.groupByAndAggregate (TsdbQuery.java:294-363),
                                   SpanCmp (TsdbQuery.java:594-621),
                                   Tags.getValueId (Tags.java:213-227)
+  plan_groups_device              the same grouping, and every group's tags, by
+                                  tsdbhip_groupby_plan on the GPU
+  SpanGroup.getTags /
+    getAggregatedTags,
+    compute_tags, span_in_range   SpanGroup.java:130-191
 
 The whole SpanGroup is evaluated by libtsdbhip on the GPU on first access
 (tsdbhip_spangroup_run); iteration then replays the reference's lazy
@@ -120,8 +125,9 @@ class Span:
     """The compacted rows of one time series, in scan order. The row
     acceptance rules of Span.addRow are applied by the library."""
 
-    def __init__(self, rows=None):
+    def __init__(self, rows=None, key=None):
         self.rows = list(rows or [])
+        self.key = None if key is None else bytes(key)  # the row key (of any of its rows: the base time is ignored)
 
     def addRow(self, row: KeyValue):
         self.rows.append(row)
@@ -232,6 +238,9 @@ class SpanGroup:
         self.downsampler = downsampler
         self._ctx = ctx
         self._result = None
+        self._tsdb = tsdb
+        self._tags_result = None  # (common, aggregated): from the device plan, else computed on first use
+        self._widths = (3, 3, 3)  # metric, tag name, tag value UID widths of the spans' keys
         if spans is not None:
             for s in spans:
                 self.add(s)
@@ -241,6 +250,7 @@ class SpanGroup:
         # assembled span; the library applies it, so every span is handed over.
         self.spans.append(span)
         self._result = None
+        self._tags_result = None
 
     def _context(self):
         if self._ctx is None:
@@ -268,6 +278,39 @@ class SpanGroup:
 
     def aggregatedSize(self):
         return self._run()[4]
+
+    def _tags(self):
+        """computeTags (SpanGroup.java:149-173): the device plan's result when
+        group_by_and_aggregate stored one, else compute_tags over the spans'
+        row keys with SpanGroup.add's time filter."""
+        if self._tags_result is None:
+            for s in self.spans:
+                if getattr(s, "key", None) is None:
+                    raise ValueError("SpanGroup.getTags: a span has no row key (Span(rows, key=...))")
+            kept = [span_in_range(s, self.start_time, self.end_time) for s in self.spans]
+            self._tags_result = compute_tags([s.key for s in self.spans], kept, *self._widths)
+        return self._tags_result
+
+    def _resolve(self, which, uid):
+        m = getattr(self._tsdb, which, None)
+        return m[uid] if m is not None else uid
+
+    def getTags(self):
+        """SpanGroup.getTags (SpanGroup.java:179-184): the tags every kept span
+        carries with one value, name id -> value id (UID bytes); names and
+        values as strings when the tsdb has tag_names / tag_values mappings."""
+        common, _ = self._tags()
+        if getattr(self._tsdb, "tag_names", None) is None or getattr(self._tsdb, "tag_values", None) is None:
+            return dict(common)
+        return {self._resolve("tag_names", k): self._resolve("tag_values", v) for k, v in common.items()}
+
+    def getAggregatedTags(self):
+        """SpanGroup.getAggregatedTags (SpanGroup.java:186-191): the first kept
+        span's tag names that are not common, in its key's order."""
+        _, agg = self._tags()
+        if getattr(self._tsdb, "tag_names", None) is None:
+            return list(agg)
+        return [self._resolve("tag_names", k) for k in agg]
 
     def size(self):
         n = 0
@@ -352,21 +395,190 @@ def plan_groups(row_keys, group_bys, metric_width=3, name_width=3, value_width=3
     return keys, order, gss
 
 
+def _parse_tags(row_key, metric_width, name_width, value_width):
+    """the (name id, value id) pairs of a row key, in key order"""
+    k = bytes(row_key)
+    pos, pairs = metric_width + 4, []
+    while pos < len(k):
+        pairs.append((k[pos:pos + name_width], k[pos + name_width:pos + name_width + value_width]))
+        pos += name_width + value_width
+    return pairs
+
+
+def compute_tags(keys, kept=None, metric_width=3, name_width=3, value_width=3):
+    """SpanGroup.computeTags (SpanGroup.java:149-173) for one group, from its
+    spans' row keys in group order; kept[i] false: SpanGroup.add filtered span
+    i out. Returns (common: {name id: value id}, aggregated: [name id]): the
+    base is the first kept span's tags; a pair is common iff every other kept
+    span has that name with that value; aggregated is the base's other names
+    (in key order; the reference's HashSet has none). A name only later spans
+    carry is reported nowhere, as in the reference."""
+    live = [k for i, k in enumerate(keys) if kept is None or kept[i]]
+    if not live:
+        return {}, []
+    base = _parse_tags(live[0], metric_width, name_width, value_width)
+    common = dict(base)
+    for k in live[1:]:
+        other = {}
+        for nm, v in _parse_tags(k, metric_width, name_width, value_width):
+            other.setdefault(nm, v)
+        for nm in [nm for nm, v in common.items() if other.get(nm) != v]:
+            del common[nm]
+    return common, [nm for nm, _ in base if nm not in common]
+
+
+def span_in_range(span, start, end):
+    """SpanGroup.add's filter (SpanGroup.java:135-139): the span's first
+    timestamp <= end and its last >= start, read from the first cell of its
+    first row and the last cell of its last row. A span without rows counts
+    as kept (its group's run reports E_EMPTY_SPAN)."""
+    rows = [r for r in span.rows if len(r.qualifier) >= 2]
+    if not rows:
+        return True
+    f, l = rows[0], rows[-1]
+    first = f.base_time + (int.from_bytes(f.qualifier[0:2], "big") >> 4)
+    last = l.base_time + (int.from_bytes(l.qualifier[-2:], "big") >> 4)
+    return first <= end and last >= start
+
+
+class GroupPlan:
+    """tsdbhip_groups_out as numpy arrays (trimmed to what the call set)."""
+
+    def __init__(self, out, order, gss, gkey, ntags, tags, common, klen, name_width, value_width):
+        G, ng = int(out.n_groups), int(out.n_grouped)
+        self.n_groups, self.n_grouped, self.n_dropped = G, ng, int(out.n_dropped)
+        self.order = order[:ng]
+        self.group_span_start = gss[:G + 1]
+        self.group_keys = [gkey[g * klen:(g + 1) * klen].tobytes() for g in range(G)]
+        self.group_ntags = ntags[:G]
+        self.group_tags = tags[:G]
+        self.group_common = common[:G]
+        self._nw, self._vw = name_width, value_width
+
+    def tags_of(self, g):
+        """(common: {name id: value id}, aggregated: [name id]) of group g"""
+        common, agg = {}, []
+        raw, pair = self.group_tags[g].tobytes(), self._nw + self._vw
+        for j in range(int(self.group_ntags[g])):
+            nm, v = raw[j * pair:j * pair + self._nw], raw[j * pair + self._nw:(j + 1) * pair]
+            if (int(self.group_common[g]) >> j) & 1:
+                common[nm] = v
+            else:
+                agg.append(nm)
+        return common, agg
+
+
+def run_groupby_plan(ctx, key_off, key_bytes, group_bys, kept=None, metric_width=3, name_width=3, value_width=3,
+                     capacity=None, device=False, n_spans=None, key_nbytes=None):
+    """Low-level: one tsdbhip_groupby_plan over row keys in SpanCmp order.
+    key_off / key_bytes / kept are numpy arrays, or with device=True device
+    addresses (ints; n_spans and key_nbytes then given). group_bys: the tag
+    name ids, sorted, or None. Returns (code, GroupPlan)."""
+    d = _abi.KeysDesc()
+    if device:
+        n, nbytes = int(n_spans), int(key_nbytes)
+        d.flags = _abi.DESC_DEVICE
+        d.key_off = C.cast(C.c_void_p(int(key_off)), _abi.P64)
+        d.key_bytes = C.cast(C.c_void_p(int(key_bytes)), _abi.P8)
+        if kept is not None:
+            d.span_kept = C.cast(C.c_void_p(int(kept)), _abi.P8)
+    else:
+        key_off = np.ascontiguousarray(key_off, np.uint64)
+        key_bytes = np.ascontiguousarray(key_bytes, np.uint8)
+        n = len(key_off) - 1 if n_spans is None else int(n_spans)
+        nbytes = len(key_bytes) if key_nbytes is None else int(key_nbytes)
+        d.key_off = _abi.ptr(key_off, C.c_uint64)
+        d.key_bytes = _abi.ptr(key_bytes, C.c_uint8)
+        if kept is not None:
+            kept = np.ascontiguousarray(kept, np.uint8)
+            d.span_kept = _abi.ptr(kept, C.c_uint8)
+    gbs = [bytes(t) for t in (group_bys or [])]
+    gb = np.frombuffer(b"".join(gbs) + b"\0", np.uint8).copy()
+    d.n_spans, d.key_nbytes = n, nbytes
+    d.metric_width, d.name_width, d.value_width = int(metric_width), int(name_width), int(value_width)
+    d.n_group_bys = len(gbs)
+    d.group_bys = _abi.ptr(gb, C.c_uint8)
+    cap = max(1, n) if capacity is None else int(capacity)
+    klen = len(gbs) * int(value_width) if 1 <= int(value_width) <= 8 else 0
+    ts = _abi.MAX_TAGS * (max(1, min(8, int(name_width))) + max(1, min(8, int(value_width))))
+    order = np.zeros(max(1, n), np.uint32)
+    gss = np.zeros(cap + 1, np.uint32)
+    gkey = np.zeros(max(1, cap * klen), np.uint8)
+    ntags = np.zeros(cap, np.uint8)
+    tags = np.zeros((cap, ts), np.uint8)
+    common = np.zeros(cap, np.uint8)
+    out = _abi.GroupsOut()
+    out.group_capacity = cap
+    out.order = _abi.ptr(order, C.c_uint32)
+    out.group_span_start = _abi.ptr(gss, C.c_uint32)
+    out.group_key = _abi.ptr(gkey, C.c_uint8)
+    out.group_ntags = _abi.ptr(ntags, C.c_uint8)
+    out.group_tags = _abi.ptr(tags, C.c_uint8)
+    out.group_common = _abi.ptr(common, C.c_uint8)
+    rc = ctx._lib.tsdbhip_groupby_plan(ctx.handle, C.byref(d), C.byref(out))
+    if rc:  # (no array was written: only the counts, which E_CAPACITY sets for a retry)
+        plan = GroupPlan.__new__(GroupPlan)
+        plan.n_groups, plan.n_grouped, plan.n_dropped = int(out.n_groups), int(out.n_grouped), int(out.n_dropped)
+        plan.raw = (order, gss, gkey, ntags, tags, common)  # the untouched output arrays
+        return rc, plan
+    return rc, GroupPlan(out, order, gss, gkey, ntags, tags, common, klen, int(name_width), int(value_width))
+
+
+def plan_groups_device(ctx, row_keys, group_bys, kept=None, metric_width=3, name_width=3, value_width=3):
+    """plan_groups on the GPU (tsdbhip_groupby_plan), with every group's tags:
+    row_keys in any order, one per span; kept[i] false: SpanGroup.add's time
+    filter drops span i from the tags (it stays in its group's batch: the
+    library applies the filter to the points itself). Returns (group_keys,
+    order, group_span_start, tags), the first three as plan_groups returns
+    them, tags[g] = (common: {name id: value id}, aggregated: [name id])."""
+    idx = sorted(range(len(row_keys)), key=lambda i: span_cmp_key(row_keys[i], metric_width))
+    keys = [bytes(row_keys[i]) for i in idx]
+    key_off = np.zeros(len(keys) + 1, np.uint64)
+    if keys:
+        key_off[1:] = np.cumsum([len(k) for k in keys])
+    key_bytes = np.frombuffer(b"".join(keys), np.uint8)
+    kept_a = None if kept is None else np.array([1 if kept[i] else 0 for i in idx], np.uint8)
+    gbs = None if group_bys is None else sorted(bytes(t) for t in group_bys)  # group_bys is sorted by id
+    rc, plan = run_groupby_plan(ctx, key_off, key_bytes, gbs, kept_a, metric_width, name_width, value_width)
+    ctx.check(rc)
+    order = [idx[j] for j in plan.order.tolist()]
+    return (plan.group_keys, order, plan.group_span_start.tolist(),
+            [plan.tags_of(g) for g in range(plan.n_groups)])
+
+
 def group_by_and_aggregate(spans, group_bys, start_time, end_time, rate, aggregator, interval=0,
-                           downsampler=None, ctx=None, metric_width=3, name_width=3, value_width=3):
+                           downsampler=None, ctx=None, metric_width=3, name_width=3, value_width=3,
+                           device_plan=False, tsdb=None):
     """TsdbQuery.groupByAndAggregate over libtsdbhip: `spans` maps row key
     bytes -> Span (findSpans' TreeMap), `group_bys` the tag-name ids to group
     by (None: one group). Returns the SpanGroups in the reference's order,
     all evaluated by one tsdbhip_spangroup_run_batch; each raises its own
-    exception lazily while iterated, like the reference's."""
+    exception lazily while iterated, like the reference's. device_plan: the
+    grouping and every group's tags by tsdbhip_groupby_plan (the default: the
+    host loop of plan_groups, tags computed on first use)."""
     keys = list(spans)
     if not keys:
         return []
-    gkeys, order, gss = plan_groups(keys, group_bys, metric_width, name_width, value_width)
-    groups = [SpanGroup(None, start_time, end_time, [spans[keys[i]] for i in order[gss[g]:gss[g + 1]]], rate,
+    for k in keys:
+        if getattr(spans[k], "key", None) is None:
+            spans[k].key = bytes(k)
+    tags = None
+    if device_plan:
+        if ctx is None:
+            ctx = SpanGroup(None, start_time, end_time, None, rate, aggregator)._context()
+        kept = [span_in_range(spans[k], start_time, end_time) for k in keys]
+        gkeys, order, gss, tags = plan_groups_device(ctx, keys, group_bys, kept, metric_width, name_width,
+                                                     value_width)
+    else:
+        gkeys, order, gss = plan_groups(keys, group_bys, metric_width, name_width, value_width)
+    groups = [SpanGroup(tsdb, start_time, end_time, [spans[keys[i]] for i in order[gss[g]:gss[g + 1]]], rate,
                         aggregator, interval, downsampler, ctx) for g in range(len(gkeys))]
     if not groups:
         return []
+    for g, grp in enumerate(groups):
+        grp._widths = (metric_width, name_width, value_width)
+        if tags is not None:
+            grp._tags_result = tags[g]
     ss = pack_spans([spans[keys[i]].rows for i in order])
     ds = downsampler is not None and interval > 0
     c = groups[0]._context()

@@ -41,6 +41,7 @@
 #include "k_direct.hip"
 #include "k_lockstep.hip"
 #include "k_group.hip"
+#include "k_groupby.hip"
 
 using namespace tsdb;
 
@@ -4335,3 +4336,5 @@ extern "C" int tsdbhip_bw_probe(tsdbhip_ctx* c, const tsdbhip_sg_desc* d, int32_
   }
   return TSDBHIP_OK;
 }
+
+#include "groupby.hip"
