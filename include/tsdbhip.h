@@ -97,6 +97,8 @@ extern "C" {
                                      on the key's buckets (k_ug_reduce runs after it) */
 #define TSDBHIP_HOT_GROUPBY    10 /* k_gb_count + scan + k_gb_scatter: the radix sort passes of
                                      tsdbhip_groupby_plan */
+#define TSDBHIP_HOT_FIND_SPANS 11 /* k_gb_count + scan + k_gb_scatter over the rows' live key
+                                     digits: the sort passes of tsdbhip_find_spans */
 #define TSDBHIP_HOT_COMPACT     4 /* k_compact_wave: every row's classification and compaction
                                      in one pass (tsdbhip_compact_rows)      */
 
@@ -470,6 +472,103 @@ int tsdbhip_groupby_plan(tsdbhip_ctx* ctx, const tsdbhip_keys_desc* keys, tsdbhi
 int tsdbhip_desc_gather(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* in, const uint32_t* order,
                         uint32_t n, tsdbhip_sg_desc* out);
 int tsdbhip_desc_gather_free(tsdbhip_ctx* ctx, tsdbhip_sg_desc* out);
+
+/* ---- findSpans: the spans of a scan (an addition to ABI v8) -------------- */
+/*
+ * tsdbhip_find_spans: the TreeMap<byte[], Span> under SpanCmp that
+ * TsdbQuery.findSpans fills row by row (TsdbQuery.java:240-285, 594-621), for
+ * the rows a scanner delivered, in delivery order (HBase delivers in full-key
+ * order; any order is accepted, as by the reference).
+ *
+ * Spans: one per distinct key under SpanCmp (metric bytes, then everything
+ * after the 4 base-time bytes), in SpanCmp order: unsigned bytes, the shorter
+ * key first on a common prefix. A span's key is the full row key of the first
+ * delivered row of that span, with that row's base time (what TreeMap.put
+ * keeps, :259-263; tsdbhip_groupby_plan ignores the base time). A row whose
+ * row_status is TSDBHIP_ROW_NONE is one for which tsdb.compact(row) returned
+ * null (:264-268): its span is still created, the row can be the one that
+ * gives the span its key, and the row is not added to the span, so a span can
+ * end up with no rows.
+ *
+ * Rows: the rows of a span keep delivery order (they are not sorted by time).
+ * Whether a row is merged, dropped or rejected is Span.addRow's business
+ * (Span.java:87-132): the SpanGroup entry points apply those rules to the
+ * descriptor they get. The five row_* outputs and span_row_start are the six
+ * arrays of a tsdbhip_sg_desc whose qual_bytes / val_bytes are the buffers the
+ * scan's offsets point into (for a compacted scan: tsdbhip_rows_out's);
+ * key_off / key_bytes are what tsdbhip_keys_desc takes.
+ *
+ * Errors: only the first offending row in delivery order counts, the message
+ * names it, and no output array is written. A key not starting with `metric`:
+ * TSDBHIP_E_ILLEGAL_DATA (:254-258). row_status TSDBHIP_ROW_ERROR:
+ * TSDBHIP_E_ILLEGAL_DATA (the exception tsdb.compact throws inside findSpans);
+ * TSDBHIP_ROW_OOB: TSDBHIP_E_OUT_OF_BOUNDS. On one row the metric check comes
+ * first, as in the reference. Not reference behaviour, TSDBHIP_E_INVALID_ARG
+ * (on one row before the two above): a width outside 1..8; a key shorter than
+ * metric_width + 4, whose tag part is no multiple of name_width + value_width
+ * or holds more than TSDBHIP_MAX_TAGS pairs; key_off decreasing or not ending
+ * at key_nbytes (the latter before any row); a row_status above
+ * TSDBHIP_ROW_OOB; for a row that is added, an odd row_qual_len or an odd
+ * row_qual_off (the tsdbhip_sg_desc rule, checked here so that a bad offset
+ * never reaches a decode kernel); a null required array; some but not all of
+ * the scan's four cell arrays. A host descriptor is checked on the host before
+ * anything is staged, a device descriptor by the first kernel, which proves
+ * every key byte inside key_bytes before reading it.
+ *
+ * No row added at all (the reference returns null, :281-283), also
+ * n_rows == 0: TSDBHIP_OK with n_spans = 0 and n_rows = 0; span_row_start[0]
+ * and key_off[0] are set to 0 when the arrays are given.
+ *
+ * n_spans > span_capacity, or the span keys needing more than key_capacity:
+ * TSDBHIP_E_CAPACITY with n_spans, n_rows, n_skipped and key_used set for a
+ * retry and no array written.
+ *
+ * tsdbhip_last_timing: total_ms, hot_ms (the sort passes), hot_kernel =
+ * TSDBHIP_HOT_FIND_SPANS, n_grid = the number of sort passes run (one per key
+ * digit position that differs between rows), alg_bytes = bytes read plus bytes
+ * written. A multi-device context runs the call on its first device.
+ */
+#define TSDBHIP_HAS_FIND_SPANS 1
+
+typedef struct tsdbhip_scan_desc {
+  uint32_t flags;             /* TSDBHIP_DESC_DEVICE: every array here AND in tsdbhip_spans_out is a
+                                 device pointer; otherwise all are host pointers */
+  uint32_t n_rows;
+  uint8_t  metric_width, name_width, value_width, reserved0;
+  uint32_t reserved1;
+  const uint8_t*  metric;       /* HOST always: metric_width bytes, the query's metric */
+  const uint64_t* key_off;      /* [n_rows+1] row r's key is key_bytes[key_off[r], key_off[r+1]) */
+  const uint8_t*  key_bytes;    /* metric | base_time(4, big-endian) | (name value)* */
+  uint64_t        key_nbytes;
+  const uint8_t*  row_status;   /* [n_rows] TSDBHIP_ROW_* as tsdbhip_compact_rows wrote them, or NULL:
+                                   every row is added */
+  /* the compacted cell of each row, as tsdbhip_rows_out lays it out; all four NULL: only the
+     order, the span boundaries and the keys are produced */
+  const uint64_t* row_qual_off; /* [n_rows] */
+  const uint32_t* row_qual_len; /* [n_rows] bytes */
+  const uint64_t* row_val_off;  /* [n_rows] */
+  const uint32_t* row_val_len;  /* [n_rows] */
+} tsdbhip_scan_desc;
+
+typedef struct tsdbhip_spans_out {
+  uint32_t  span_capacity;     /* in */
+  uint32_t  n_spans;           /* out (also on E_CAPACITY) */
+  uint32_t  n_rows;            /* out: rows added (the reference's nrows) */
+  uint32_t  n_skipped;         /* out: rows with status NONE */
+  uint64_t  key_capacity;      /* in: bytes in key_bytes (key_nbytes of the input always suffices) */
+  uint64_t  key_used;          /* out */
+  uint32_t* row_order;         /* [scan n_rows] delivery index of output row i; first n_rows valid */
+  uint64_t* span_row_start;    /* [span_capacity+1] */
+  uint32_t* row_base;          /* [scan n_rows] base time read from the row key */
+  uint32_t* row_ncells;        /* row_qual_len / 2 */
+  uint64_t* row_qual_off;      /* passed through: the byte buffers are the caller's, untouched */
+  uint64_t* row_val_off;
+  uint32_t* row_val_len;
+  uint64_t* key_off;           /* [span_capacity+1] } exactly what tsdbhip_keys_desc takes */
+  uint8_t*  key_bytes;         /* [key_capacity]    } */
+} tsdbhip_spans_out;
+
+int tsdbhip_find_spans(tsdbhip_ctx* ctx, const tsdbhip_scan_desc* scan, tsdbhip_spans_out* out);
 
 /* ---- output formatting (host cores, no GPU) ----------------------------- */
 /*

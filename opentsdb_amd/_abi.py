@@ -205,6 +205,53 @@ class GroupsOut(C.Structure):
     ]
 
 
+HOT_FIND_SPANS = 11
+HOT_NAMES[HOT_FIND_SPANS] = "k_gb_count+scan+k_gb_scatter (find_spans)"
+
+
+class ScanDesc(C.Structure):
+    """tsdbhip_scan_desc: the scanned rows for tsdbhip_find_spans"""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("n_rows", C.c_uint32),
+        ("metric_width", C.c_uint8),
+        ("name_width", C.c_uint8),
+        ("value_width", C.c_uint8),
+        ("reserved0", C.c_uint8),
+        ("reserved1", C.c_uint32),
+        ("metric", P8),
+        ("key_off", P64),
+        ("key_bytes", P8),
+        ("key_nbytes", C.c_uint64),
+        ("row_status", P8),
+        ("row_qual_off", P64),
+        ("row_qual_len", P32),
+        ("row_val_off", P64),
+        ("row_val_len", P32),
+    ]
+
+
+class SpansOut(C.Structure):
+    """tsdbhip_spans_out: the spans (arrays owned by the caller, host or device as the scan's)"""
+    _fields_ = [
+        ("span_capacity", C.c_uint32),
+        ("n_spans", C.c_uint32),
+        ("n_rows", C.c_uint32),
+        ("n_skipped", C.c_uint32),
+        ("key_capacity", C.c_uint64),
+        ("key_used", C.c_uint64),
+        ("row_order", P32),
+        ("span_row_start", P64),
+        ("row_base", P32),
+        ("row_ncells", P32),
+        ("row_qual_off", P64),
+        ("row_val_off", P64),
+        ("row_val_len", P32),
+        ("key_off", P64),
+        ("key_bytes", P8),
+    ]
+
+
 def ptr(arr, ctype):
     """numpy array -> ctypes pointer (array must stay alive)."""
     return arr.ctypes.data_as(C.POINTER(ctype))

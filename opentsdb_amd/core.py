@@ -590,6 +590,192 @@ def group_by_and_aggregate(spans, group_bys, start_time, end_time, rate, aggrega
     return groups
 
 
+# --------------------------------------------------------------- findSpans ----
+def find_spans(rows, metric, metric_width=3, name_width=3, value_width=3):
+    """TsdbQuery.findSpans (TsdbQuery.java:240-285) restated on the host:
+    `rows` is a list of (row_key, KeyValue | None) in the order the scanner
+    delivered them, None standing for a row tsdb.compact(row) returned null
+    for. Returns {row key: Span} in SpanCmp order, the key being the full row
+    key of the span's first delivered row (what TreeMap.put keeps) and the
+    span's rows in delivery order, or None when no row was added (:281-283).
+    A key that does not start with `metric`: IllegalDataException (:254-258)."""
+    metric = bytes(metric)
+    spans, nrows = {}, 0  # by SpanCmp key, in insertion order
+    for i, (k, kv) in enumerate(rows):
+        k = bytes(k)
+        if k[:metric_width] != metric[:metric_width]:
+            raise IllegalDataException(f"HBase returned a row that doesn't match our scanner: row {i} does not "
+                                       f"start with {list(metric)}")
+        span = spans.get(span_cmp_key(k, metric_width))
+        if span is None:
+            span = spans[span_cmp_key(k, metric_width)] = Span(key=k)
+        if kv is not None:  # Can be null if we ignored all KVs.
+            span.addRow(kv)
+            nrows += 1
+    if nrows == 0:
+        return None
+    return {spans[c].key: spans[c] for c in sorted(spans)}
+
+
+class FoundSpans:
+    """tsdbhip_spans_out as numpy arrays (trimmed to what the call set); on
+    an error only the counts, and .raw = the untouched output arrays."""
+
+    FIELDS = ("row_order", "span_row_start", "row_base", "row_ncells", "row_qual_off", "row_val_off",
+              "row_val_len", "key_off", "key_bytes")
+
+    def __init__(self, out, arrays, ok):
+        self.n_spans, self.n_rows, self.n_skipped = int(out.n_spans), int(out.n_rows), int(out.n_skipped)
+        self.key_used = int(out.key_used)
+        self.raw = arrays
+        if not ok:
+            return
+        S, R = self.n_spans, self.n_rows
+        for f in self.FIELDS:
+            a = arrays.get(f)
+            if a is None or isinstance(a, int):
+                setattr(self, f, None)
+            elif f in ("span_row_start", "key_off"):
+                setattr(self, f, a[:S + 1])
+            elif f == "key_bytes":
+                setattr(self, f, a[:self.key_used])
+            else:
+                setattr(self, f, a[:R])
+
+    def keys(self):
+        kb = self.key_bytes.tobytes()
+        return [kb[int(self.key_off[s]):int(self.key_off[s + 1])] for s in range(self.n_spans)]
+
+
+def run_find_spans(ctx, key_off, key_bytes, metric, status=None, cells=None, metric_width=3, name_width=3,
+                   value_width=3, span_capacity=None, key_capacity=None, device=False, n_rows=None,
+                   key_nbytes=None, outputs=None):
+    """Low-level: one tsdbhip_find_spans over rows in delivery order.
+    key_off / key_bytes / status and cells = (qual_off, qual_len, val_off,
+    val_len) are numpy arrays, or with device=True device addresses (ints;
+    n_rows and key_nbytes then given, and outputs = {field: device address} of
+    the caller's output arrays, span_capacity / key_capacity their sizes).
+    outputs may also pre-fill host arrays (the tests' sentinels). Returns
+    (code, FoundSpans)."""
+    d = _abi.ScanDesc()
+    keep = []
+
+    def inp(a, dtype, ptype):
+        if a is None:
+            return None
+        if device:
+            return C.cast(C.c_void_p(int(a)), ptype)
+        a = np.ascontiguousarray(a, dtype)
+        keep.append(a)
+        return a.ctypes.data_as(ptype)
+
+    if device:
+        n, nbytes = int(n_rows), int(key_nbytes)
+        d.flags = _abi.DESC_DEVICE
+    else:
+        n = (len(key_off) - 1 if key_off is not None else 0) if n_rows is None else int(n_rows)
+        nbytes = (len(key_bytes) if key_bytes is not None else 0) if key_nbytes is None else int(key_nbytes)
+    ko, kb, st = inp(key_off, np.uint64, _abi.P64), inp(key_bytes, np.uint8, _abi.P8), inp(status, np.uint8, _abi.P8)
+    if ko is not None:
+        d.key_off = ko
+    if kb is not None:
+        d.key_bytes = kb
+    if st is not None:
+        d.row_status = st
+    if cells is not None:
+        for f, a, dt, pt in zip(("row_qual_off", "row_qual_len", "row_val_off", "row_val_len"), cells,
+                                (np.uint64, np.uint32, np.uint64, np.uint32),
+                                (_abi.P64, _abi.P32, _abi.P64, _abi.P32)):
+            p = inp(a, dt, pt)
+            if p is not None:
+                setattr(d, f, p)
+    m = np.frombuffer(bytes(metric) + b"\0" * 8, np.uint8).copy()
+    d.metric = _abi.ptr(m, C.c_uint8)
+    d.n_rows, d.key_nbytes = n, nbytes
+    d.metric_width, d.name_width, d.value_width = int(metric_width), int(name_width), int(value_width)
+    scap = max(1, n) if span_capacity is None else int(span_capacity)
+    kcap = max(1, nbytes) if key_capacity is None else int(key_capacity)
+    out = _abi.SpansOut()
+    out.span_capacity, out.key_capacity = scap, kcap
+    types = {"row_order": (np.uint32, _abi.P32, max(1, n)), "span_row_start": (np.uint64, _abi.P64, scap + 1),
+             "row_base": (np.uint32, _abi.P32, max(1, n)), "row_ncells": (np.uint32, _abi.P32, max(1, n)),
+             "row_qual_off": (np.uint64, _abi.P64, max(1, n)), "row_val_off": (np.uint64, _abi.P64, max(1, n)),
+             "row_val_len": (np.uint32, _abi.P32, max(1, n)), "key_off": (np.uint64, _abi.P64, scap + 1),
+             "key_bytes": (np.uint8, _abi.P8, max(1, kcap))}
+    arrays = {}
+    for f, (dt, pt, size) in types.items():
+        if device:
+            a = (outputs or {}).get(f)
+            if a is not None:
+                arrays[f] = int(a)
+                setattr(out, f, C.cast(C.c_void_p(int(a)), pt))
+            continue
+        if outputs is not None and f in outputs:
+            a = outputs[f]
+            if a is None:  # (a null output array, for the argument checks)
+                arrays[f] = None
+                continue
+        elif cells is None and f in ("row_ncells", "row_qual_off", "row_val_off", "row_val_len"):
+            continue
+        else:
+            a = np.zeros(size, dt)
+        assert a.dtype == dt and a.flags.c_contiguous
+        arrays[f] = a
+        setattr(out, f, a.ctypes.data_as(pt))
+    rc = ctx._lib.tsdbhip_find_spans(ctx.handle, C.byref(d), C.byref(out))
+    return rc, FoundSpans(out, arrays, rc == 0)
+
+
+def _pack_keys(rows):
+    """(key_off, key_bytes, status) of find_spans' rows"""
+    keys = [bytes(k) for k, _ in rows]
+    key_off = np.zeros(len(keys) + 1, np.uint64)
+    if keys:
+        key_off[1:] = np.cumsum([len(k) for k in keys])
+    key_bytes = np.frombuffer(b"".join(keys), np.uint8).copy()
+    status = np.array([_abi.ROW_NONE if kv is None else _abi.ROW_SINGLE for _, kv in rows], np.uint8)
+    return key_off, key_bytes, status
+
+
+def _pack_scan(rows):
+    """(key_off, key_bytes, status, cells, qual_bytes, val_bytes) of find_spans'
+    rows, the compacted cells packed in delivery order as pack_spans lays them out"""
+    key_off, key_bytes, status = _pack_keys(rows)
+    ss = pack_spans([[kv if kv is not None else KeyValue(0, b"", b"") for _, kv in rows]])
+    cells = (ss.row_qual_off, (ss.row_ncells * 2).astype(np.uint32), ss.row_val_off, ss.row_val_len)
+    return key_off, key_bytes, status, cells, ss.qual_bytes, ss.val_bytes
+
+
+def find_spans_device(ctx, rows, metric, metric_width=3, name_width=3, value_width=3):
+    """find_spans on the GPU (tsdbhip_find_spans): the same dict, or None."""
+    key_off, key_bytes, status = _pack_keys(rows)
+    rc, fs = run_find_spans(ctx, key_off, key_bytes, metric, status, None, metric_width, name_width, value_width)
+    if rc:
+        raise _exception_for(rc, ctx.last_error())
+    if fs.n_rows == 0:
+        return None
+    srs, order, out = fs.span_row_start.tolist(), fs.row_order.tolist(), {}
+    for s, k in enumerate(fs.keys()):
+        out[k] = Span([rows[r][1] for r in order[srs[s]:srs[s + 1]]], key=k)
+    return out
+
+
+def query_run(ctx, rows, metric, group_bys, start_time, end_time, rate, aggregator, interval=0, downsampler=None,
+              metric_width=3, name_width=3, value_width=3, device=False, tsdb=None):
+    """TsdbQuery.run (TsdbQuery.java:225-227): groupByAndAggregate(findSpans())
+    over the rows of a scan (find_spans' `rows`). device: findSpans by
+    tsdbhip_find_spans and the grouping by tsdbhip_groupby_plan; otherwise the
+    host restatements. The SpanGroups are evaluated on the GPU either way."""
+    if device:
+        spans = find_spans_device(ctx, rows, metric, metric_width, name_width, value_width)
+    else:
+        spans = find_spans(rows, metric, metric_width, name_width, value_width)
+    if spans is None:
+        return []
+    return group_by_and_aggregate(spans, group_bys, start_time, end_time, rate, aggregator, interval, downsampler,
+                                  ctx, metric_width, name_width, value_width, device_plan=device, tsdb=tsdb)
+
+
 # ------------------------------------------------------------ output text ----
 FMT_ASCII, FMT_GNUPLOT, FMT_CLI = 0, 1, 2
 

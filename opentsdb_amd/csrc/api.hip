@@ -42,6 +42,7 @@
 #include "k_lockstep.hip"
 #include "k_group.hip"
 #include "k_groupby.hip"
+#include "k_findspans.hip"
 
 using namespace tsdb;
 
@@ -4338,3 +4339,4 @@ extern "C" int tsdbhip_bw_probe(tsdbhip_ctx* c, const tsdbhip_sg_desc* d, int32_
 }
 
 #include "groupby.hip"
+#include "findspans.hip"
