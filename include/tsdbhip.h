@@ -204,6 +204,13 @@ typedef struct tsdbhip_timing {
                                           kernels, one host round trip        */
 #define TSDBHIP_PATH_UNIFORM_FALLBACK 32u  /* the uniform aligned group did not
                                           stand: the general path ran the call */
+#define TSDBHIP_PATH_GROUP_DIRECT 64u  /* the aligned group of one-row spans ran
+                                          straight from the descriptor: no
+                                          assembly, no kept list, no host round
+                                          trip before the streaming kernel    */
+#define TSDBHIP_PATH_GROUP_DIRECT_FALLBACK 128u  /* it was tried and the group
+                                          did not stand: the call ran again
+                                          from assembly                       */
 
 /* ---- row compaction (CompactionQueue.compact) -------------------------- */
 /*
@@ -340,6 +347,11 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *   "lockstep"      "on" | "off" | "always"   the lockstep proposal (k_lockstep):
  *                   "on" for groups of >= 2048 lockstep waves (and sharded
  *                   groups), "always" for any group
+ *   "group_direct"  "on" | "off" | "always"   the aligned group of one-row spans
+ *                   launched with no assembly before it (as many rows as spans,
+ *                   an aligned-group query): "on" for groups of more than 4096
+ *                   spans, "always" for any group; a group that is not one runs
+ *                   again from assembly (TSDBHIP_PATH_GROUP_DIRECT*)
  *   "timing_detail" "on" | "off"   decode / grid event pairs in tsdbhip_timing
  *   "check_clean"   "on" | "off"   check the zero-on-entry invariants (stderr)
  *   "events"        "kernel" | "marker" | "none"   how tsdbhip_timing is measured:

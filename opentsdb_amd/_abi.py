@@ -13,6 +13,8 @@ PATH_LOCKSTEP = 4  # k_lockstep: one pass over the qualifiers and values of a lo
 PATH_DIRECT_REDO = 8  # its proposal did not hold: the call ran again on the proven path
 PATH_UNIFORM = 16  # every kept span proposed one class key at assembly: G from the key, one round trip
 PATH_UNIFORM_FALLBACK = 32  # the uniform aligned group did not stand: the general path ran the call
+PATH_GROUP_DIRECT = 64  # the aligned group of one-row spans ran straight from the descriptor (no assembly)
+PATH_GROUP_DIRECT_FALLBACK = 128  # it was tried and did not stand: the call ran again from assembly
 
 OK = 0
 E_ILLEGAL_DATA = -1

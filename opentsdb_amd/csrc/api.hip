@@ -67,6 +67,8 @@ struct Options {
   int decode = DEC_AUTO;       // "decode": the decode / downsample path forced
   bool aligned_group = true;   // "aligned_group": k_ds_reg's aligned-group reduction may be tried
   int lockstep = 1;            // "lockstep": "off" (0), "on" (1: groups big enough), "always" (2)
+  int group_direct = 1;        // "group_direct": the aligned group of one-row spans launched with no assembly:
+                               // "off" (0), "on" (1: more than KC_MAX spans), "always" (2)
   bool timing_detail = false;  // "timing_detail": decode / grid event pairs (tsdbhip_timing)
   bool check_clean = false;    // "check_clean": verify the zero-on-entry invariants (stderr)
   int events = 0;              // "events": timing events on kernel launches (0), marker packets (1), none (2)
@@ -567,6 +569,10 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
   else if (n == "lockstep") {
     ok = v == "on" || v == "off" || v == "always";
     o.lockstep = v == "off" ? 0 : (v == "on" ? 1 : 2);
+  }
+  else if (n == "group_direct") {
+    ok = v == "on" || v == "off" || v == "always";
+    o.group_direct = v == "off" ? 0 : (v == "on" ? 1 : 2);
   }
   else if (n == "timing_detail") ok = on_off(o.timing_detail);
   else if (n == "check_clean") ok = on_off(o.check_clean);
@@ -1779,7 +1785,99 @@ DEVI void ug_fap_tail_spec(const FapArgs& fap, const UgTail& t) {
   __syncthreads();
   small_snap(sm, t.snap, s_ok ? t.init : nullptr, t.seq);
 }
-template <int AGG, bool SPEC>
+// the direct launch's tail (ds_reg_direct_body: no assembly ran): the class
+// key, the verdict, kk and nb from the call state's fap_key; what assembly and
+// the kept list would have published (every span kept: n_kept, n_input) is
+// written here when the group is one. A sibling of ug_fap_tail_spec, not a
+// mode of it or of ug_fap_tail (see k_ug_ds_reg on folding tails).
+DEVI void ug_fap_tail_direct(const FapArgs& fap, const UgTail& t) {
+  __shared__ int64_t s_acc[4][WAVE];
+  const uint32_t tid = threadIdx.x, lane = tid % WAVE, w = tid / WAVE;
+  Small* sm = t.sm;
+  const unsigned long long k1 = coherent_load(&sm->fap_key[0]), k2 = coherent_load(&sm->fap_key[2]);
+  // (one class, every span in it; else this rank's partials neutral and its
+  // validity 0, as k_fap_neutral64's)
+  const bool one = !coherent_load(&sm->fap_broken) && k1 == coherent_load(&sm->fap_key[1]) &&
+                   k2 == coherent_load(&sm->fap_key[3]) && (k2 >> 32) != 0;
+  const uint32_t t0 = (uint32_t)(k1 >> 32), ncell = (uint32_t)k1, step = (uint32_t)(k2 >> 32);
+  const uint32_t n_kept = one ? t.n_kept : 0u;
+  const uint32_t kk0 = one ? (uint32_t)((t.interval + step - 1) / step) : 1u;
+  const uint32_t nbk = one ? (ncell + kk0 - 1) / kk0 : 0u;
+  const int op = t.op;
+  const int64_t neutral = fap_neutral(op);
+  auto comb = [&](int64_t x, int64_t y) { return op == 0 ? ladd(x, y) : (op == 1 ? min(x, y) : max(x, y)); };
+  int64_t acc = neutral;
+  {  // (coherent loads, all in flight together; the copies reset to neutral after)
+    int64_t v[UG_NCOPY / 4];
+#pragma unroll
+    for (uint32_t i = 0; i < UG_NCOPY / 4; i++)
+      v[i] = (int64_t)coherent_load(fap.copies + (uint64_t)(w + 4 * i) * WAVE + lane);
+#pragma unroll
+    for (uint32_t i = 0; i < UG_NCOPY / 4; i++) {
+      acc = comb(acc, v[i]);
+      fap.copies[(uint64_t)(w + 4 * i) * WAVE + lane] = (unsigned long long)neutral;
+    }
+  }
+  s_acc[w][lane] = acc;
+  __syncthreads();
+  __shared__ uint32_t s_ok;
+  if (w == 0) {
+    acc = comb(comb(s_acc[0][lane], s_acc[1][lane]), comb(s_acc[2][lane], s_acc[3][lane]));
+    const bool in = lane < nbk;
+    if (in) {
+      const uint32_t sb = lane * kk0, m = min(sb + kk0, ncell) - sb;
+      t.grid[lane] = t0 + sb * step + (uint32_t)((uint64_t)step * (m - 1) / 2);
+    }
+    const bool v = one && coherent_load(&sm->err) == ERR_NONE && nbk > 0 && nbk <= WAVE &&
+                   coherent_load(&sm->gflags[0]) == 0;
+    if (lane == 0) {
+      sm->T = nbk;
+      sm->fap_valid = v ? 1ull : 0ull;
+      s_ok = v ? 1u : 0u;
+      if (one) {  // (the kept-list kernel's counts: every span kept, n cells each)
+        sm->n_kept = n_kept;
+        sm->n_input = (unsigned long long)n_kept * ncell;
+      }
+    }
+    if (t.sharded) {
+      t.p_i[lane] = in ? acc : neutral;
+      t.p_cnt[lane] = in ? n_kept : 0u;
+      if (lane < t.pack.n) {
+        if (t.pack.field[lane] == (void*)&sm->fap_valid) {
+          t.pack.buf[lane] = v ? 1ull : 0ull;
+        } else if (lane == 4 || lane == 5 || lane == 10 || lane == 11) {
+          // (the class key's header words, as the speculative tail's: ~0 / 0
+          // for a rank without a group)
+          const uint64_t a1 = one ? k1 : ~0ull, a2 = one ? k2 : 0ull;
+          const uint64_t val = (lane == 4 || lane == 10) ? a1 : a2;
+          t.pack.buf[lane] = t.pack.kind[lane] == 4 ? ~val : val;
+        } else {
+          xmove_one(t.pack, lane);
+        }
+      }
+    } else if (v && in) {
+      Acc a;
+      acc_init(a);
+      a.cnt = n_kept;
+      a.ia = acc;
+      switch (t.agg) {
+        case 1: finalize_one<1, MODE_INT, false>(t.fo, lane, a); break;
+        case 2: finalize_one<2, MODE_INT, false>(t.fo, lane, a); break;
+        case 3: finalize_one<3, MODE_INT, false>(t.fo, lane, a); break;
+        default: finalize_one<0, MODE_INT, false>(t.fo, lane, a); break;
+      }
+    }
+  }
+  __syncthreads();
+  if (t.sharded) return;
+  // the finish, as ug_fap_tail's
+  if (s_ok && tid == 0) sm->fap_done = 1;
+  __syncthreads();
+  small_snap(sm, t.snap, s_ok ? t.init : nullptr, t.seq);
+}
+// (DIRECT: the launch with no assembly before it, ds_reg_direct_body; a
+// template argument of its own, so the other instantiations carry none of it)
+template <int AGG, bool SPEC, bool DIRECT = false>
 #ifndef UG_LDS_CAP
 #define UG_LDS_CAP 40960u  // (build knob) LDS a k_ug_ds_reg block claims: 40 KB = 4 blocks a CU
 #endif
@@ -1800,7 +1898,8 @@ k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
     if (t.sharded && blockIdx.x == 0) ug_fap_tail_spec(fap, t);
     return;
   }
-  ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
+  if constexpr (DIRECT) ds_reg_direct_body<AGG>(a, ncells, vlen, fap);
+  else ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
   __shared__ uint32_t s_last;
   __builtin_amdgcn_s_waitcnt(0);  // (this wave's atomics acknowledged)
   __syncthreads();
@@ -1810,7 +1909,8 @@ k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
   // (two tails: the host-sized one is the code the unsharded C3* launch was
   // measured with — folding the speculative logic into it cost that launch
   // ~2.5 %, same box, through the whole kernel's code generation)
-  if (SPEC) ug_fap_tail_spec(fap, t);
+  if constexpr (DIRECT) ug_fap_tail_direct(fap, t);
+  else if (SPEC) ug_fap_tail_spec(fap, t);
   else ug_fap_tail(fap, t);
 }
 
@@ -1915,6 +2015,11 @@ static std::vector<Fld> partial_fields(const ReduceArgs& r, uint64_t off, int ag
 //    off the cadence: RC_UG_FALLBACK after the call (results dropped).
 constexpr int RC_REDO = 1000;  // a lockstep proposal did not hold: the proven path runs the call
 constexpr int RC_UG_FALLBACK = 1001;
+// the direct aligned group did not stand: the call runs again from assembly
+// (unsharded: every proposal open; sharded, _X: the general path, as every
+// other rank's RC_UG_FALLBACK)
+constexpr int RC_GD_FALLBACK = 1002;
+constexpr int RC_GD_FALLBACK_X = 1003;
 struct UgIn {
   const tsdbhip_sg_desc* d;
   Xchg* X;
@@ -1932,6 +2037,8 @@ struct UgIn {
   bool e;            // (unsharded, downsampled) k_ds_reg's E + k_reduce's aligned spans
   bool spec;         // (aligned group, sharded) launched before the host read the call state:
                      // n_kept is the span count, the group's verdict and key come from the device
+  bool direct;       // (aligned group) launched with no assembly before it (ds_reg_direct_body): n_kept is
+                     // the span count = the row count, the verdict, key and counts come from the device
 };
 
 // The E variant's pieces a span (at most `want`): k_ds_reg's wave p takes
@@ -1985,8 +2092,9 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
   const int32_t I = d->ds_interval;
   // (a rank making no attempt may hold no key: step 0; speculative: the
   // device's key)
-  const uint32_t kk = u.mine && !u.spec ? (uint32_t)(((int64_t)I + step - 1) / step) : 1u;
-  const uint32_t nb = u.mine && !u.spec ? (n + kk - 1) / kk : 0u;
+  const bool dev_key = u.spec || u.direct;
+  const uint32_t kk = u.mine && !dev_key ? (uint32_t)(((int64_t)I + step - 1) / step) : 1u;
+  const uint32_t nb = u.mine && !dev_key ? (n + kk - 1) / kk : 0u;
   const int fop = agg == TSDBHIP_AGG_MIN ? 1 : (agg == TSDBHIP_AGG_MAX ? 2 : 0);
   uint32_t* gridv = scratch<uint32_t>(ctx, "grid", WAVE);
   int64_t* o_pi = scratch<int64_t>(ctx, "fo_i", WAVE);
@@ -2065,9 +2173,20 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
                    ? (unsigned)at.sharedSizeBytes
                    : 21000u;
       }();
+      // (the direct instantiation's own static LDS: the block claims exactly UG_LDS_CAP)
+      static const unsigned stat_lds_direct = [] {
+        hipFuncAttributes at = {};
+        return hipFuncGetAttributes(&at, (const void*)k_ug_ds_reg<A, false, true>) == hipSuccess
+                   ? (unsigned)at.sharedSizeBytes
+                   : 21000u;
+      }();
       const unsigned pad = stat_lds < UG_LDS_CAP ? UG_LDS_CAP - stat_lds : 0u;
+      const unsigned pad_direct = stat_lds_direct < UG_LDS_CAP ? UG_LDS_CAP - stat_lds_direct : 0u;
       EV_START(ctx, 8);
-      if (u.spec)
+      if (u.direct)
+        LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ug_ds_reg<A, false, true>), dim3(rblocks), dim3(256), pad_direct, st, u.da, gr,
+                    u.row_ncells, u.row_val_len, fa, t);
+      else if (u.spec)
         LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ug_ds_reg<A, true>), dim3(rblocks), dim3(256), pad, st, u.da, gr,
                     u.row_ncells, u.row_val_len, fa, t);
       else
@@ -2113,13 +2232,13 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
     HIPCHK(hipStreamSynchronize(st));
     check_stamp(ctx, seq2);
     ctx->sm_ready = true;
-    return RC_UG_FALLBACK;
+    return u.direct ? (sharded ? RC_GD_FALLBACK_X : RC_GD_FALLBACK) : RC_UG_FALLBACK;
   }
   ctx->sm_ready = true;
   const uint64_t T = h.T;
   out->n_input_points = h.n_input;
   tm.n_grid = T;
-  tm.paths |= TSDBHIP_PATH_ALIGNED_GROUP;
+  tm.paths |= TSDBHIP_PATH_ALIGNED_GROUP | (u.direct ? TSDBHIP_PATH_GROUP_DIRECT : 0u);
   if (sharded) {
     tm.n_collectives = X->n_coll;
     tm.x_bytes = X->x_bytes;
@@ -2423,7 +2542,7 @@ struct SgCall {
   Slot* ctx;
   const tsdbhip_sg_desc* d;
   tsdbhip_sg_out* out;
-  bool ls_allow, ug_allow;
+  bool ls_allow, ug_allow, gd_allow;
   // begin
   bool dev = false, exact = false, sharded = false, rate = false, check_clean = false, bm_clean = false;
   bool tgd_clean = false, tgd_used = false, detail = false;
@@ -2507,10 +2626,11 @@ struct SgCall {
   uint8_t* o_isint = nullptr;
   FinalArgs fin_map;
 
-  SgCall(Slot* c, const tsdbhip_sg_desc* dd, tsdbhip_sg_out* o, bool ls, bool ug)
-      : ctx(c), d(dd), out(o), ls_allow(ls), ug_allow(ug) {}
+  SgCall(Slot* c, const tsdbhip_sg_desc* dd, tsdbhip_sg_out* o, bool ls, bool ug, bool gd)
+      : ctx(c), d(dd), out(o), ls_allow(ls), ug_allow(ug), gd_allow(gd) {}
   int run() {
     begin();
+    if (group_direct_q()) return group_direct_try();
     assemble();
     int rc = sync1();
     if (rc != RC_CONTINUE) return rc;
@@ -2589,6 +2709,37 @@ struct SgCall {
     g_ev_pend_i = -1;
     std::memset(ctx->ev_alias, 0xff, sizeof ctx->ev_alias);
     EV_START(ctx, 0);
+  }
+
+  // ---- the direct aligned group: the call's first kernel is the streaming
+  // kernel itself, over the descriptor (ds_reg_direct_body) — no assembly,
+  // no kept list, no host round trip before it. Decided from what the host
+  // holds: the aligned group's query (ug_fap_q below) over as many rows as
+  // spans, in a group beyond KC_MAX spans (the one whose assembly is
+  // k_assemble_tiles + k_kept_scatter_tiles); "always": any size. A group
+  // that is not one row a span on one class costs a fraction of a pass (the
+  // blocks leave once the group is broken) and the call runs again from
+  // assembly; sharded, the rank issues the speculative launch's collectives.
+  bool group_direct_q() const {
+    const int gd = ctx->opt.group_direct;
+    return gd_allow && ug_allow && gd != 0 && ctx->opt.decode == DEC_AUTO && interval > 0 && !rate && ds_agg <= 3 &&
+           agg <= 3 && !exact && ctx->opt.aligned_group && !ctx->opt.timing_detail && S > 0 && R == S &&
+           (gd == 2 || S > KC_MAX);
+  }
+  int group_direct_try() {
+    std::memset(&da, 0, sizeof da);
+    da.span_row_start = span_row_start; da.row_base = row_base; da.row_qual_off = row_qual_off;
+    da.row_val_off = row_val_off; da.qual = qual; da.val = val; da.n_kept = S; da.row_ncells = row_ncells;
+    da.row_val_len = row_val_len; da.start = d->start_time; da.end = d->end_time; da.interval = interval;
+    da.ds_agg = ds_agg; da.rate = 0; da.err = &sm->err; da.gflags = sm->gflags; da.range = sm->range;
+    da.fstar = &sm->fstar; da.span0 = sharded ? d->span0 : 0;
+    UgIn u = {};
+    u.d = d; u.X = X; u.sm = sm; u.da = da; u.row_ncells = row_ncells; u.row_val_len = row_val_len;
+    u.n_kept = S; u.lockstep = false; u.mine = true; u.direct = true;
+    const int rc = uniform_run(ctx, u, out, tm);
+    ctx->bitmap_clean = bm_clean;  // (no bitmap touched)
+    ctx->tgdone_clean = tgd_clean;
+    return rc;
   }
 
   void assemble() {
@@ -3739,8 +3890,8 @@ struct SgCall {
 };
 
 static int spangroup_run_once(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_out* out, bool ls_allow,
-                              bool ug_allow) {
-  SgCall c(ctx, d, out, ls_allow, ug_allow);
+                              bool ug_allow, bool gd_allow) {
+  SgCall c(ctx, d, out, ls_allow, ug_allow, gd_allow);
   return c.run();
 }
 
@@ -3755,10 +3906,18 @@ static int spangroup_run_once(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_ou
 //                                            not hold (test_uniform.py:67)
 //   NO_UNIFORM --RC_REDO-------> PROVEN      the general path's lockstep proposal
 //                                            did not hold (test_lockstep.py)
+//   FIRST    --RC_GD_FALLBACK--> FULL        the direct aligned group (no assembly)
+//                                            did not stand, unsharded
+//                                            (test_group_direct.py: *fell_back*)
+//   FIRST    --RC_GD_FALLBACK_X-> NO_UNIFORM the same on a rank of a sharded call:
+//                                            where the other ranks' RC_UG_FALLBACK
+//                                            takes them (the same collectives)
+// FIRST is FULL with the direct aligned group allowed: a call that is not
+// eligible for it runs as FULL and has FULL's edges.
 // PROVEN tries no proposal and so ends the call. A rerun stages nothing
 // again: the host-resident inputs the first attempt copied are still in HBM
 // (ADVICE r5).
-enum SgAttempt { SG_FULL, SG_NO_UNIFORM, SG_PROVEN, SG_DONE };
+enum SgAttempt { SG_FIRST, SG_FULL, SG_NO_UNIFORM, SG_PROVEN, SG_DONE };
 struct SgEdge {
   SgAttempt from;
   int rc;
@@ -3766,6 +3925,10 @@ struct SgEdge {
   uint32_t path;  // (tsdbhip_timing.paths)
 };
 static const SgEdge kSgEdges[] = {
+    {SG_FIRST, RC_GD_FALLBACK, SG_FULL, TSDBHIP_PATH_GROUP_DIRECT_FALLBACK},
+    {SG_FIRST, RC_GD_FALLBACK_X, SG_NO_UNIFORM, TSDBHIP_PATH_GROUP_DIRECT_FALLBACK | TSDBHIP_PATH_UNIFORM_FALLBACK},
+    {SG_FIRST, RC_UG_FALLBACK, SG_NO_UNIFORM, TSDBHIP_PATH_UNIFORM_FALLBACK},
+    {SG_FIRST, RC_REDO, SG_PROVEN, TSDBHIP_PATH_DIRECT_REDO},
     {SG_FULL, RC_UG_FALLBACK, SG_NO_UNIFORM, TSDBHIP_PATH_UNIFORM_FALLBACK},
     {SG_FULL, RC_REDO, SG_PROVEN, TSDBHIP_PATH_DIRECT_REDO},
     {SG_NO_UNIFORM, RC_REDO, SG_PROVEN, TSDBHIP_PATH_DIRECT_REDO},
@@ -3779,15 +3942,15 @@ static int spangroup_run(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_out* ou
   ctx->reuse_inputs = false;
   uint32_t paths = 0;
   int rc = 0;
-  for (SgAttempt a = SG_FULL; a != SG_DONE;) {
-    rc = spangroup_run_once(ctx, d, out, a != SG_PROVEN, a == SG_FULL);
+  for (SgAttempt a = SG_FIRST; a != SG_DONE;) {
+    rc = spangroup_run_once(ctx, d, out, a != SG_PROVEN, a == SG_FIRST || a == SG_FULL, a == SG_FIRST);
     SgAttempt next = SG_DONE;
     for (const SgEdge& e : kSgEdges)
       if (e.from == a && e.rc == rc) {
         next = e.to;
         paths |= e.path;
       }
-    if (next == SG_DONE && (rc == RC_REDO || rc == RC_UG_FALLBACK)) {  // (an attempt that may not rerun)
+    if (next == SG_DONE && (rc == RC_REDO || rc == RC_UG_FALLBACK || rc == RC_GD_FALLBACK || rc == RC_GD_FALLBACK_X)) {  // (an attempt that may not rerun)
       set_error(ctx, "spangroup_run: rerun code %d with no edge from attempt %d", rc, (int)a);
       throw Fail{TSDBHIP_E_HIP};
     }

@@ -381,6 +381,9 @@ __device__ void span_ds_general(const DecodeArgs& a, uint32_t k, int64_t* s_bits
     int64_t prev_ts = -1;
     bool unsorted = false, anyf = false, anyi = false;
     int64_t bad = -1;
+    // the span's first bad cell: at or past the `short` overflow it is the
+    // iterator's ArrayIndexOutOfBounds, before it an illegal value length
+    int64_t bad_cell = -1;
     uint64_t ecount = 0;
     bool open = false;
     Bucket cb;  // carried open bucket (wave-uniform)
@@ -401,6 +404,8 @@ __device__ void span_ds_general(const DecodeArgs& a, uint32_t k, int64_t* s_bits
       anyf |= fmask != 0;
       anyi |= (emask & ~fmask) != 0;
       const uint64_t badmask = ballot(o.in_e && !o.okv);
+      if (bad_cell < 0 && badmask) bad_cell = (int64_t)c0 + __builtin_ctzll(badmask);
+      const int64_t bad_code = ovf >= 0 && bad_cell >= ovf ? BAD_OOB : BAD_ILLEGAL;
       // ---- greedy bucket chain (Span.java:389-398) ----
       uint64_t starts = 0;
       int64_t E = open ? cb.end : INT64_MIN;
@@ -419,7 +424,7 @@ __device__ void span_ds_general(const DecodeArgs& a, uint32_t k, int64_t* s_bits
       if (open && !cont) {
         // the carried bucket ended exactly at the chunk boundary: emit it
         if (lane == 0 && ecount < cap) finalize_bucket<AGG>(a, cb, ecount, eo);
-        if (bad < 0 && cb.bad) bad = ((int64_t)ecount << 4) | BAD_ILLEGAL;
+        if (bad < 0 && cb.bad) bad = ((int64_t)ecount << 4) | bad_code;
         ecount++;
         open = false;
       }
@@ -499,7 +504,7 @@ __device__ void span_ds_general(const DecodeArgs& a, uint32_t k, int64_t* s_bits
         if (eidx < cap) finalize_bucket<AGG>(a, b, eidx, eo);
       }
       const uint64_t bl = ballot(lane < nclosed && b.bad);
-      if (bad < 0 && bl) bad = ((int64_t)(ecount + __builtin_ctzll(bl)) << 4) | BAD_ILLEGAL;
+      if (bad < 0 && bl) bad = ((int64_t)(ecount + __builtin_ctzll(bl)) << 4) | bad_code;
       ecount += nclosed;
       // carry the last (open) segment
       if (!span_end && nseg > 0) {

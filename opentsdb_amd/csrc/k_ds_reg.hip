@@ -111,7 +111,9 @@ DEVI uint32_t lv_ix(uint32_t c) {
 // chunk's loads in flight while one is processed, as ds_span); buckets that
 // close in these rows go to E. Returns true if the premise breaks. The
 // caller checked the rows (reg_rows_ok) and that ra starts a bucket.
-template <int AGG, int W, bool FLT>
+// (CELL0 false: the direct aligned group's one-row spans, whose row starts
+// the span at cell 0 — there is no row_cell0 to read)
+template <int AGG, int W, bool FLT, bool CELL0 = true>
 DEVI bool reg_piece(const DecodeArgs& a, const RegSpan& sp, uint64_t ra, uint64_t rb, const uint32_t* ncells,
                     uint64_t* L_v, int64_t* BK, int fop, int64_t* part) {
   constexpr bool PREFIX = (AGG == 0 || AGG == 3) && !FLT;  // wrapping sums: prefix differences
@@ -125,7 +127,7 @@ DEVI bool reg_piece(const DecodeArgs& a, const RegSpan& sp, uint64_t ra, uint64_
     p.qoff = sld(&a.row_qual_off[r]);
     p.voff = sld(&a.row_val_off[r]);
     p.base = sld(&a.row_base[r]);
-    p.cell0 = sld(&a.row_cell0[r]);
+    p.cell0 = CELL0 ? sld(&a.row_cell0[r]) : 0u;
     p.c0 = 0;
     p.done = false;
     return p;
@@ -152,7 +154,7 @@ DEVI bool reg_piece(const DecodeArgs& a, const RegSpan& sp, uint64_t ra, uint64_
   bool bad = false;
   int64_t carry = 0;  // the open bucket's value over its cells in earlier chunks
   // bucket of the next chunk's first cell and that cell's place in it
-  uint32_t bcur = sp.dkk.div(sld(&a.row_cell0[ra])), ph = 0;
+  uint32_t bcur = CELL0 ? sp.dkk.div(sld(&a.row_cell0[ra])) : 0u, ph = 0;
   uint32_t fbase = bcur;  // first bucket held in BK
   uint32_t bclosed = bcur;  // buckets closed so far: [.., bclosed)
   // decode + qualifier check + LDS staging of one chunk (FULL: 512 cells)
@@ -514,8 +516,108 @@ DEVI void ds_reg_body(const DecodeArgs& a, const SpanDsArgs& g, const uint32_t* 
   }
 }
 
+// The direct aligned group: k_ug_ds_reg's body for a group whose every span
+// is one row, launched with no assembly before it (a.n_kept spans = rows;
+// wave k takes span k). What assembly would have established for such a span
+// — one RowSeq of n cells, kept, no Q1 seek, no `short` overflow, its E
+// capacity, its class key — follows from the row's five fields and its first
+// qualifier word; every other qualifier is proven by reg_piece as it streams.
+// A span that is anything else (no row or several, a float, another width,
+// a cell outside [start, end], > 64 buckets, ...) marks the group broken and
+// the call runs again from assembly, which also reports any error: this
+// kernel raises none. The class key in fap.key is the uniform proposal's
+// (x0 << 32 | n, step << 32 | q0), so a sharded rank on this path agrees with
+// one on the speculative path. A wave that finds the group already broken
+// skips its span (scalar load; a stale 0 only streams a span for nothing).
+template <int AGG>
+DEVI void ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap) {
+  __shared__ uint64_t s_v[4][DCH];
+  __shared__ int64_t s_bk[4][WAVE];
+  __shared__ int64_t s_part[WAVE];
+  const int lane = lane_id();
+  const uint32_t wib = ufl(threadIdx.x / WAVE);
+  const uint32_t s = blockIdx.x * 4u + wib;
+  const int fop = fap.op;
+  if (threadIdx.x < WAVE) s_part[threadIdx.x] = fap_neutral(fop);
+  __syncthreads();
+  const int64_t I = a.interval;
+  const bool mine = s < a.n_kept;
+  // (scalar loads and a wave-uniform verdict, as ds_reg_body's prologue.
+  // Measured and rejected: the row's fields loaded at index s, span s being
+  // row s in such a group, together with the span's row range and the flag —
+  // one round trip for three; the avg instantiation then spilled to scratch,
+  // 48 B a lane, and the C3* kernel ran 6.177 ms against 6.121, same box.)
+  bool ok = mine && I > 0 && sld(fap.broken) == 0;
+  uint32_t W = 0, q0 = 0;
+  RegSpan sp = {};
+  uint64_t r0 = 0;
+  if (ok) {
+    r0 = sld(&a.span_row_start[s]);
+    ok = sld(&a.span_row_start[s + 1]) == r0 + 1 && r0 < a.n_kept;
+  }
+  if (ok) {
+    const uint32_t nc = sld(&ncells[r0]), vl = sld(&vlen[r0]);
+    const uint64_t qo = sld(&a.row_qual_off[r0]), vo = sld(&a.row_val_off[r0]);
+    const uint32_t vb = vl - 1;  // (nc >= 2: a compacted row ends with its meta byte)
+    W = nc >= 2 ? vb / nc : 0;
+    // (vb < 32768: RowSeq.Iterator's `short` value index, assemble_fast_one)
+    ok = nc >= 2 && vl != 0 && (W == 8 || W == 4) && vb == W * nc && vb < 32768u && (qo & 7) == 0 && (vo & 15) == 0;
+    if (ok) {
+      const uint32_t w = sld((const uint32_t*)(a.qual + qo));  // cells 0 and 1, big-endian
+      const uint32_t q1 = ((w >> 16) & 0xFF) << 8 | (w >> 24);
+      q0 = ((w & 0xFF) << 8) | ((w >> 8) & 0xFF);
+      const int64_t d0 = q0 >> 4, st = (int64_t)(q1 >> 4) - d0;
+      const int64_t first = (int64_t)sld(&a.row_base[r0]) + d0;
+      const int64_t span = (int64_t)(nc - 1) * st, last = first + span;
+      // integer cells of width W; the cadence; no seek, nothing past `end`
+      // (every span kept whole); every delta inside the row's 4096 s
+      ok = (q0 & 15u) == W - 1 && st >= 1 && first >= a.start && last <= a.end && last <= 0xFFFFFFFFll &&
+           d0 + span <= 4095;
+      if (ok) {
+        sp.n = nc;
+        sp.t0 = (uint32_t)first;
+        sp.step = (uint32_t)st;
+        sp.kk = (uint32_t)((I + st - 1) / st);
+        sp.dkk.init(sp.kk);
+        const uint32_t nb = (nc + sp.kk - 1) / sp.kk;
+        // (assemble_finish's E capacity of the kept span: first >= start)
+        const uint32_t cap = min(nc, (uint32_t)span / (uint32_t)I + 1u);
+        ok = nb <= WAVE && nb <= cap;
+      }
+    }
+  }
+  if (ok) {
+    const bool fail = W == 8 ? reg_piece<AGG, 8, false, false>(a, sp, r0, r0 + 1, ncells, s_v[wib], s_bk[wib], fop, s_part)
+                             : reg_piece<AGG, 4, false, false>(a, sp, r0, r0 + 1, ncells, s_v[wib], s_bk[wib], fop, s_part);
+    ok = !fail;
+  }
+  if (mine && lane == 0) {  // the group's class: one key, no span outside it
+    if (!ok) {
+      if (!*(volatile uint32_t*)fap.broken) atomicOr(fap.broken, 1u);
+    } else {
+      const unsigned long long k1 = ((unsigned long long)sp.t0 << 32) | sp.n;
+      const unsigned long long k2 = ((unsigned long long)sp.step << 32) | q0;
+      volatile unsigned long long* kv = fap.key;
+      if (k1 < kv[0]) atomicMin(&fap.key[0], k1);
+      if (k1 > kv[1]) atomicMax(&fap.key[1], k1);
+      if (k2 < kv[2]) atomicMin(&fap.key[2], k2);
+      if (k2 > kv[3]) atomicMax(&fap.key[3], k2);
+    }
+  }
+  __syncthreads();  // the block's partial into its copy
+  if (threadIdx.x < WAVE) {
+    const int64_t v = s_part[threadIdx.x];
+    if (v != fap_neutral(fop)) {
+      unsigned long long* c = fap.copies + (uint64_t)(blockIdx.x % fap.ncopy) * WAVE + threadIdx.x;
+      if (fop == 0) atomicAdd(c, (unsigned long long)v);
+      else if (fop == 1) atomicMin((long long*)c, (long long)v);
+      else atomicMax((long long*)c, (long long)v);
+    }
+  }
+}
+
 #ifndef DS_WPE
-#define DS_WPE 7  // waves per SIMD the register allocation aims at (C2, same box: the compiler's 83 VGPRs
+#define DS_WPE 7 // waves per SIMD the register allocation aims at (C2, same box: the compiler's 83 VGPRs
                   // 0.165 ms, 7: 0.150, 8: 0.161)
 #endif
 template <int AGG>
