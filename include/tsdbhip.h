@@ -352,6 +352,10 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *                   an aligned-group query): "on" for groups of more than 4096
  *                   spans, "always" for any group; a group that is not one runs
  *                   again from assembly (TSDBHIP_PATH_GROUP_DIRECT*)
+ *   "group_direct_run" "auto" | "1" | "2" | "4" | "8" | "16" | "32"   spans a wave
+ *                   of that launch streams as one run (wave g of G: spans g,
+ *                   g + G, ...); "auto": 32 where the group still gives 16384
+ *                   runs, else 16 or 8, else 1
  *   "timing_detail" "on" | "off"   decode / grid event pairs in tsdbhip_timing
  *   "check_clean"   "on" | "off"   check the zero-on-entry invariants (stderr)
  *   "events"        "kernel" | "marker" | "none"   how tsdbhip_timing is measured:

@@ -69,6 +69,8 @@ struct Options {
   int lockstep = 1;            // "lockstep": "off" (0), "on" (1: groups big enough), "always" (2)
   int group_direct = 1;        // "group_direct": the aligned group of one-row spans launched with no assembly:
                                // "off" (0), "on" (1: more than KC_MAX spans), "always" (2)
+  int group_direct_run = 0;    // "group_direct_run": spans a wave of the direct group streams as one run:
+                               // "auto" (0: ug_direct_run()), or 1, 2, 4, 8, 16, 32
   bool timing_detail = false;  // "timing_detail": decode / grid event pairs (tsdbhip_timing)
   bool check_clean = false;    // "check_clean": verify the zero-on-entry invariants (stderr)
   int events = 0;              // "events": timing events on kernel launches (0), marker packets (1), none (2)
@@ -573,6 +575,10 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
   else if (n == "group_direct") {
     ok = v == "on" || v == "off" || v == "always";
     o.group_direct = v == "off" ? 0 : (v == "on" ? 1 : 2);
+  }
+  else if (n == "group_direct_run") {
+    ok = v == "auto" || v == "1" || v == "2" || v == "4" || v == "8" || v == "16" || v == "32";
+    o.group_direct_run = v == "auto" ? 0 : std::atoi(v.c_str());
   }
   else if (n == "timing_detail") ok = on_off(o.timing_detail);
   else if (n == "check_clean") ok = on_off(o.check_clean);
@@ -1898,8 +1904,12 @@ k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
     if (t.sharded && blockIdx.x == 0) ug_fap_tail_spec(fap, t);
     return;
   }
-  if constexpr (DIRECT) ds_reg_direct_body<AGG>(a, ncells, vlen, fap);
-  else ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
+  if constexpr (DIRECT) {
+    // (the body counts its block done itself: one barrier pair per 4 runs)
+    if (ds_reg_direct_body<AGG>(a, ncells, vlen, fap, &t.sm->ug_done)) ug_fap_tail_direct(fap, t);
+    return;
+  }
+  ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
   __shared__ uint32_t s_last;
   __builtin_amdgcn_s_waitcnt(0);  // (this wave's atomics acknowledged)
   __syncthreads();
@@ -1909,8 +1919,7 @@ k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
   // (two tails: the host-sized one is the code the unsharded C3* launch was
   // measured with — folding the speculative logic into it cost that launch
   // ~2.5 %, same box, through the whole kernel's code generation)
-  if constexpr (DIRECT) ug_fap_tail_direct(fap, t);
-  else if (SPEC) ug_fap_tail_spec(fap, t);
+  if (SPEC) ug_fap_tail_spec(fap, t);
   else ug_fap_tail(fap, t);
 }
 
@@ -2075,6 +2084,23 @@ static uint32_t ug_e_pieces(uint32_t t0, uint32_t step, uint32_t n, uint32_t kk,
   return 1;
 }
 
+// Spans a wave of the direct group (ds_reg_direct_body) takes as one run: the
+// grid is sized for it, ceil(n_kept / 4 run) blocks, and wave g takes every
+// span g + k * (4 blocks). "auto": UG_RUN spans (C3*, one box: 1 / 4 / 8 / 16 /
+// 32 spans 6.29 / 6.33 / 6.22 / 6.07 / 5.96 ms a step) where that
+// still leaves UG_RUN_FILL runs — 4 times the 4096 waves resident on 256 CUs
+// at 4 blocks each, so that the launch's last, partly filled round stays a
+// small part of it — else the largest power of two below it that does; runs
+// of 2 and 4 measured no faster than none, so below 8 a wave takes one span
+// (a small group: as many waves as it has spans).
+constexpr uint32_t UG_RUN = 32, UG_RUN_FILL = 16384;
+static uint32_t ug_direct_run(int opt, uint32_t n_kept) {
+  if (opt > 0) return (uint32_t)opt;
+  uint32_t r = UG_RUN;
+  while (r > 1 && n_kept / r < UG_RUN_FILL) r >>= 1;
+  return r >= 8 ? r : 1u;
+}
+
 // the aligned group (k_ug_ds_reg; sharded: one collective group and
 // k_fap_finish_end); RC_UG_FALLBACK when the group did not stand
 static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbhip_timing& tm) {
@@ -2130,7 +2156,9 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
   } else {
     // k_ds_reg, a wave a span, in the aligned group's mode, with the tail
     // in its last block (k_ug_ds_reg)
-    const uint32_t rblocks = (n_kept + 3) / 4;
+    // (direct: a wave takes a run of spans)
+    const uint32_t run = u.direct ? ug_direct_run(ctx->opt.group_direct_run, n_kept) : 1u;
+    const uint32_t rblocks = (uint32_t)(((uint64_t)n_kept + 4 * run - 1) / (4 * run));
     SpanDsArgs gr = {};
     gr.nseg = CK_NSEG;
     gr.seg_cap = 4u * ((rblocks + CK_NSEG - 1) / CK_NSEG);
@@ -3943,7 +3971,15 @@ static int spangroup_run(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_out* ou
   uint32_t paths = 0;
   int rc = 0;
   for (SgAttempt a = SG_FIRST; a != SG_DONE;) {
-    rc = spangroup_run_once(ctx, d, out, a != SG_PROVEN, a == SG_FIRST || a == SG_FULL, a == SG_FIRST);
+    try {
+      rc = spangroup_run_once(ctx, d, out, a != SG_PROVEN, a == SG_FIRST || a == SG_FULL, a == SG_FIRST);
+    } catch (Fail&) {
+      // (an attempt that ends the call with an error has written no timing:
+      // the call's is the edges taken so far, not the call's before it)
+      ctx->timing = tsdbhip_timing{};
+      ctx->timing.paths = paths;
+      throw;
+    }
     SgAttempt next = SG_DONE;
     for (const SgEdge& e : kSgEdges)
       if (e.from == a && e.rc == rc) {

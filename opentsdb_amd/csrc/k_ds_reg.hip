@@ -517,103 +517,347 @@ DEVI void ds_reg_body(const DecodeArgs& a, const SpanDsArgs& g, const uint32_t* 
 }
 
 // The direct aligned group: k_ug_ds_reg's body for a group whose every span
-// is one row, launched with no assembly before it (a.n_kept spans = rows;
-// wave k takes span k). What assembly would have established for such a span
-// — one RowSeq of n cells, kept, no Q1 seek, no `short` overflow, its E
-// capacity, its class key — follows from the row's five fields and its first
-// qualifier word; every other qualifier is proven by reg_piece as it streams.
-// A span that is anything else (no row or several, a float, another width,
-// a cell outside [start, end], > 64 buckets, ...) marks the group broken and
-// the call runs again from assembly, which also reports any error: this
-// kernel raises none. The class key in fap.key is the uniform proposal's
-// (x0 << 32 | n, step << 32 | q0), so a sharded rank on this path agrees with
-// one on the speculative path. A wave that finds the group already broken
-// skips its span (scalar load; a stale 0 only streams a span for nothing).
-template <int AGG>
-DEVI void ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap) {
-  __shared__ uint64_t s_v[4][DCH];
-  __shared__ int64_t s_bk[4][WAVE];
-  __shared__ int64_t s_part[WAVE];
+// is one row, launched with no assembly before it (a.n_kept spans = rows).
+// What assembly would have established for such a span — one RowSeq of n
+// cells, kept, no Q1 seek, no `short` overflow, its E capacity, its class key
+// — follows from the row's five fields and its first qualifier word; every
+// other qualifier is proven as the span streams. A span that is anything else
+// (no row or several, a float, another width, a cell outside [start, end],
+// > 64 buckets, ...) marks the group broken and the call runs again from
+// assembly, which also reports any error: this kernel raises none. The class
+// key in fap.key is the uniform proposal's (x0 << 32 | n, step << 32 | q0), so
+// a sharded rank on this path agrees with one on the speculative path.
+//
+// A wave takes a run of spans, as one stream of chunks: wave g of the launch's
+// G waves takes spans g, g + G, g + 2 G, ... (the host sizes the grid for the
+// run length it wants), so that the waves resident at one time still read
+// neighbouring spans (runs of consecutive spans measured slower than no runs,
+// DESIGN.md §5). While a span streams, the run's next span's fields and first
+// qualifier word are loaded (scalar, a stage a chunk step), and its first
+// chunk goes into the register set that the present span's last chunk but one
+// frees, so from its first load to its run's last step the wave has a chunk
+// in flight. Every span of a run has to be of the first one's
+// class (the group stands on one class only, so another class breaks it
+// whoever sees it): the run keeps one RegSpan, a span's own state is its two
+// offsets. Spans s of such a group being rows s, the fields are read at index
+// s together with the span's row range, which has to be [s, s + 1).
+// The wave combines its spans' buckets in a register (lane b: bucket b), the
+// block its waves' in LDS: one set of partial atomics and one count on `done`
+// per 4 runs. A wave that finds the group broken, or breaks it, leaves
+// the rest of its run (a stale 0 only streams spans for nothing).
+struct DirSpan {
+  uint64_t rs0, rs1, qo, vo;
+  uint32_t nc, vl, base, brk, w;
+};
+// row s's fields, span s's row range and the flag: one round trip
+DEVI void dir_load(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap, uint32_t s,
+                   DirSpan& d) {
+  d.rs0 = sld(&a.span_row_start[s]);
+  d.rs1 = sld(&a.span_row_start[s + 1]);
+  d.nc = sld(&ncells[s]);
+  d.vl = sld(&vlen[s]);
+  d.qo = sld(&a.row_qual_off[s]);
+  d.vo = sld(&a.row_val_off[s]);
+  d.base = sld(&a.row_base[s]);
+  d.brk = sld(fap.broken);
+}
+// ... checked (0: not a member; else the cell width), the first qualifier word
+// loaded. (vb < 32768: RowSeq.Iterator's `short` value index, assemble_fast_one)
+DEVI uint32_t dir_fields(const DecodeArgs& a, uint32_t s, DirSpan& d) {
+  const uint32_t vb = d.vl - 1;  // (nc >= 2: a compacted row ends with its meta byte)
+  const uint32_t W = d.nc >= 2 ? vb / d.nc : 0;
+  const bool ok = d.brk == 0 && d.rs0 == s && d.rs1 == (uint64_t)s + 1 && d.nc >= 2 && d.vl != 0 && (W == 8 || W == 4) &&
+                  vb == W * d.nc && vb < 32768u && (d.qo & 7) == 0 && (d.vo & 15) == 0;
+  if (!ok) return 0;
+  d.w = sld((const uint32_t*)(a.qual + d.qo));  // cells 0 and 1, big-endian
+  return W;
+}
+// ... and the span's class key (k1, k2; false: not a member): integer cells
+// of width W; the cadence; no seek, nothing past `end` (every span kept
+// whole); every delta inside the row's 4096 s
+DEVI bool dir_key(const DecodeArgs& a, const DirSpan& d, uint32_t W, uint64_t& k1, uint64_t& k2) {
+  const uint32_t q1 = ((d.w >> 16) & 0xFF) << 8 | (d.w >> 24);
+  const uint32_t q0 = ((d.w & 0xFF) << 8) | ((d.w >> 8) & 0xFF);
+  const int64_t d0 = q0 >> 4, st = (int64_t)(q1 >> 4) - d0;
+  const int64_t first = (int64_t)d.base + d0;
+  const int64_t span = (int64_t)(d.nc - 1) * st, last = first + span;
+  k1 = ((uint64_t)first << 32) | d.nc;
+  k2 = ((uint64_t)st << 32) | q0;
+  return (q0 & 15u) == W - 1 && st >= 1 && first >= a.start && last <= a.end && last <= 0xFFFFFFFFll &&
+         d0 + span <= 4095;
+}
+
+// Java long / int toward zero for 1 <= n <= 4096 (a bucket's cells: a row
+// spans 4096 s), inline — ldiv64_32's general case is a call, which would
+// drain the chunk loads in flight at every span end: the high 32 bits first,
+// what is left with the low ones is below n 2^32 <= 2^44, where udiv64_32's
+// refined double reciprocal (error < 1) and one correction step are exact.
+DEVI int64_t ldiv64_4096(int64_t a, uint32_t n) {
+  const uint64_t ua = a < 0 ? (uint64_t)0 - (uint64_t)a : (uint64_t)a;
+  const double dn = (double)n;
+  double r = __builtin_amdgcn_rcp(dn);
+  r = __builtin_fma(r, __builtin_fma(-dn, r, 1.0), r);  // one Newton step
+  auto div = [&](uint64_t x) {  // x < 2^44
+    uint64_t q = (uint64_t)__builtin_floor((double)x * r);
+    const int64_t rem = (int64_t)(x - q * (uint64_t)n);
+    if (rem < 0) q--;
+    else if (rem >= (int64_t)n) q++;
+    return q;
+  };
+  const uint64_t qh = div(ua >> 32);
+  const uint64_t rh = (ua >> 32) - qh * n;
+  const uint64_t q = (qh << 32) + div((rh << 32) | (uint32_t)ua);
+  return a < 0 ? (int64_t)((uint64_t)0 - q) : (int64_t)q;
+}
+
+// The run s, s + stride, ... < s1 of one wave, span s's checks passed (d0; the class sp, k1,
+// k2; row base `base`): reg_piece's chunk stream for integer one-row spans
+// that all start at cell 0 with <= 64 buckets (so the bucket buffer BK holds a
+// whole span, bucket b at BK[b]), carried on across the spans of the run.
+// `acc` takes the spans' buckets (lane b: bucket b; fop: 0 wrapping add,
+// 1 min, 2 max). Returns false when a span of the run is not a member.
+template <int AGG, int W>
+DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap,
+                  const RegSpan& sp, uint32_t base, uint64_t k1, uint64_t k2, const DirSpan& d0, uint32_t s,
+                  uint32_t s1, uint64_t* L_v, int64_t* BK, int fop, int64_t& acc) {
+  constexpr bool PREFIX = AGG == 0 || AGG == 3;  // wrapping sums: prefix differences
   const int lane = lane_id();
-  const uint32_t wib = ufl(threadIdx.x / WAVE);
-  const uint32_t s = blockIdx.x * 4u + wib;
-  const int fop = fap.op;
-  if (threadIdx.x < WAVE) s_part[threadIdx.x] = fap_neutral(fop);
-  __syncthreads();
-  const int64_t I = a.interval;
-  const bool mine = s < a.n_kept;
-  // (scalar loads and a wave-uniform verdict, as ds_reg_body's prologue.
-  // Measured and rejected: the row's fields loaded at index s, span s being
-  // row s in such a group, together with the span's row range and the flag —
-  // one round trip for three; the avg instantiation then spilled to scratch,
-  // 48 B a lane, and the C3* kernel ran 6.177 ms against 6.121, same box.)
-  bool ok = mine && I > 0 && sld(fap.broken) == 0;
-  uint32_t W = 0, q0 = 0;
-  RegSpan sp = {};
-  uint64_t r0 = 0;
-  if (ok) {
-    r0 = sld(&a.span_row_start[s]);
-    ok = sld(&a.span_row_start[s + 1]) == r0 + 1 && r0 < a.n_kept;
-  }
-  if (ok) {
-    const uint32_t nc = sld(&ncells[r0]), vl = sld(&vlen[r0]);
-    const uint64_t qo = sld(&a.row_qual_off[r0]), vo = sld(&a.row_val_off[r0]);
-    const uint32_t vb = vl - 1;  // (nc >= 2: a compacted row ends with its meta byte)
-    W = nc >= 2 ? vb / nc : 0;
-    // (vb < 32768: RowSeq.Iterator's `short` value index, assemble_fast_one)
-    ok = nc >= 2 && vl != 0 && (W == 8 || W == 4) && vb == W * nc && vb < 32768u && (qo & 7) == 0 && (vo & 15) == 0;
-    if (ok) {
-      const uint32_t w = sld((const uint32_t*)(a.qual + qo));  // cells 0 and 1, big-endian
-      const uint32_t q1 = ((w >> 16) & 0xFF) << 8 | (w >> 24);
-      q0 = ((w & 0xFF) << 8) | ((w >> 8) & 0xFF);
-      const int64_t d0 = q0 >> 4, st = (int64_t)(q1 >> 4) - d0;
-      const int64_t first = (int64_t)sld(&a.row_base[r0]) + d0;
-      const int64_t span = (int64_t)(nc - 1) * st, last = first + span;
-      // integer cells of width W; the cadence; no seek, nothing past `end`
-      // (every span kept whole); every delta inside the row's 4096 s
-      ok = (q0 & 15u) == W - 1 && st >= 1 && first >= a.start && last <= a.end && last <= 0xFFFFFFFFll &&
-           d0 + span <= 4095;
-      if (ok) {
-        sp.n = nc;
-        sp.t0 = (uint32_t)first;
-        sp.step = (uint32_t)st;
-        sp.kk = (uint32_t)((I + st - 1) / st);
-        sp.dkk.init(sp.kk);
-        const uint32_t nb = (nc + sp.kk - 1) / sp.kk;
-        // (assemble_finish's E capacity of the kept span: first >= start)
-        const uint32_t cap = min(nc, (uint32_t)span / (uint32_t)I + 1u);
-        ok = nb <= WAVE && nb <= cap;
+  const uint32_t fl = (uint32_t)(W - 1);
+  const uint32_t n = sp.n, kk = sp.kk;
+  const uint32_t nb = sp.dkk.div(n + kk - 1);
+  struct Pos {
+    uint64_t qo, vo;
+    uint32_t c0;
+    bool done;
+  };
+  // the next span of the run: nst 0 nothing loaded, 1 its fields in flight,
+  // 2 its fields checked (nw) and its qualifier word in flight
+  const uint32_t stride = 4u * gridDim.x;  // the launch's waves: the run's spans lie that far apart
+  auto after = [&](uint32_t x) { return x + stride < x ? s1 : min(x + stride, s1); };
+  uint32_t nx = after(s), nst = 0, nw = 0;
+  DirSpan nd = {};
+  bool member = true;
+  auto tick = [&]() {
+    if (nx >= s1) return;
+    if (nst == 0) {
+      dir_load(a, ncells, vlen, fap, nx, nd);
+      nst = 1;
+    } else if (nst == 1) {
+      nw = dir_fields(a, nx, nd);
+      nst = 2;
+    }
+  };
+  auto advance = [&](const Pos& p) {
+    Pos q = p;
+    if (p.done) return q;
+    if (p.c0 + DCH < n) {
+      q.c0 += DCH;
+      return q;
+    }
+    q.done = true;
+    if (nx < s1) {
+      while (nst < 2) tick();
+      uint64_t n1 = 0, n2 = 0;
+      if (nw == (uint32_t)W && dir_key(a, nd, nw, n1, n2) && n1 == k1 && n2 == k2) {
+        q.qo = nd.qo;
+        q.vo = nd.vo;
+        q.c0 = 0;
+        q.done = false;
+        nx = after(nx);
+        nst = 0;
+      } else {
+        member = false;
+        nx = s1;
       }
     }
+    return q;  // (done: the same chunk again — its load stays in the row)
+  };
+  RawW<W> A, B;
+  auto issue = [&](const Pos& p, RawW<W>& x) {
+    const uint32_t c = p.c0 + 8u * lane;
+    __builtin_amdgcn_s_setprio(2);
+    load_raw<W>(a, p.qo, p.vo, c < n ? c : (n - 1) & ~7u, x);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  bool bad = false;
+  int64_t carry = 0;    // the open bucket's value over its cells in earlier chunks
+  uint32_t bcur = 0, ph = 0;  // bucket of the next chunk's first cell and that cell's place in it
+  // decode + qualifier check + LDS staging of one chunk (FULL: 512 cells)
+  auto stage = [&](auto full, const RawW<W>& cur, uint32_t nv, uint32_t cs) {
+    constexpr bool FULL = decltype(full)::value;
+    const uint32_t nmine = FULL ? 8u : (nv > 8u * lane ? min(8u, nv - 8u * lane) : 0u);
+    {  // (t0 + c step - base) << 4 | flags, two cells per dword
+      const uint32_t dd = sp.t0 + (cs + 8u * lane) * sp.step - base;
+      uint32_t e = ((dd << 4) | fl) * 0x00010001u + (sp.step << 20);
+      const uint32_t inc = sp.step * 0x00200020u;
+      const uint32_t qw[4] = {cur.q.x, cur.q.y, cur.q.z, cur.q.w};
+      uint32_t miss = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        uint32_t x = qpair(qw[i]) ^ e;
+        if (!FULL) x &= nmine >= 2u * i + 2 ? 0xFFFFFFFFu : (nmine == 2u * i + 1 ? 0x0000FFFFu : 0u);
+        miss |= x;
+        e += inc;
+      }
+      bad |= miss != 0;
+    }
+    uint64_t pv = 0, pvi[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      int64_t bits = raw_value<W>(cur, j);
+      if (!FULL && (uint32_t)j >= nmine) bits = 0;
+      pv += (uint64_t)bits;
+      pvi[j] = PREFIX ? pv : (uint64_t)bits;
+    }
+    const uint64_t xv = PREFIX ? wave_incl_scan_u64_dpp(pv) - pv : 0ull;
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+      ulonglong2 v2;
+      v2.x = pvi[j] + xv;
+      v2.y = pvi[j + 1] + xv;
+      *(ulonglong2*)&L_v[8 * lane + 2 * (((uint32_t)(j >> 1) + ((uint32_t)lane >> 1)) & 3u)] = v2;
+    }
+  };
+  auto step = [&](const Pos& p, const RawW<W>& cur) {
+    const uint32_t cs = ufl(p.c0);  // span cell index of the chunk start
+    const uint32_t nv = ufl(min(DCH, n - cs));
+    if (cs == 0) {  // a span begins
+      carry = 0;
+      bcur = 0;
+      ph = 0;
+    }
+    if (nv == DCH) stage(std::integral_constant<bool, true>(), cur, nv, cs);
+    else stage(std::integral_constant<bool, false>(), cur, nv, cs);
+    wave_lds_sync();
+    // ---- buckets ending in [cs, cend), then the one still open at cend ----
+    const uint32_t cend = cs + nv;
+    const uint32_t adv = sp.dkk.div(ph + nv);  // buckets whose last cell is in the chunk (full ones)
+    const uint32_t b_lo = bcur;
+    const uint32_t b_end = cend == n ? nb : b_lo + adv;  // first bucket not closed here
+    ph = ph + nv - adv * kk;
+    bcur = b_lo + adv;
+    const bool open = cend < n && ph != 0;  // bucket b_end takes later cells
+    const uint32_t nclose = b_end - b_lo;
+    const uint32_t ntot = nclose + (open ? 1u : 0u);
+    int64_t carry_next = 0;
+    for (uint32_t jb = 0; jb < ntot; jb += WAVE) {
+      const uint32_t j = jb + lane;
+      const bool act = j < ntot;
+      const uint32_t b = b_lo + (act ? j : 0u);
+      const uint32_t sb = b * kk;
+      const uint32_t eb = act && j < nclose ? min(sb + kk, n) - 1 : cend - 1;  // (open: its cells so far)
+      const uint32_t la = sb > cs ? sb - cs : 0u, lb = eb - cs;
+      const bool cont = sb < cs;  // began in an earlier chunk
+      int64_t v;
+      if (PREFIX) {
+        v = (int64_t)(L_v[lv_ix(lb)] - (la > 0 ? L_v[lv_ix(la - 1)] : 0ull));
+        if (cont) v = ladd(v, carry);
+      } else {
+        v = cont ? carry : (int64_t)L_v[lv_ix(la)];
+        for (uint32_t i = cont ? la : la + 1; act && i <= lb; i++) v = ds_combine<AGG>(v, (int64_t)L_v[lv_ix(i)]);
+      }
+      if (act && j < nclose) BK[b] = v;  // (b < nb <= 64)
+      if (open && jb + WAVE >= ntot) carry_next = (int64_t)readlane_u64((uint64_t)v, (int)(ntot - 1 - jb));
+    }
+    carry = carry_next;
+    wave_lds_sync();
+    if (cend == n && ballot(bad) == 0 && (uint32_t)lane < nb) {  // the span's buckets, a lane each (avg: its division)
+      const uint32_t sb = (uint32_t)lane * kk, m = min(sb + kk, n) - sb;
+      const int64_t v = AGG == 3 ? ldiv64_4096(BK[lane], m) : BK[lane];
+      acc = fop == 0 ? ladd(acc, v) : (fop == 1 ? min(acc, v) : max(acc, v));
+    }
+  };
+  Pos p0 = {d0.qo, d0.vo, 0u, false};
+  Pos p1 = advance(p0);
+  issue(p0, A);
+  issue(p1, B);
+  for (;;) {
+    tick();
+    step(p0, A);
+    if (p1.done || ballot(bad) != 0) break;
+    const Pos p2 = advance(p1);
+    issue(p2, A);
+    tick();
+    step(p1, B);
+    if (p2.done || ballot(bad) != 0) break;
+    const Pos p3 = advance(p2);
+    issue(p3, B);
+    p0 = p2;
+    p1 = p3;
+  }
+  return member && ballot(bad) == 0;
+}
+
+// Returns true in every thread of the launch's last block to finish.
+template <int AGG>
+DEVI bool ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap,
+                             uint32_t* done) {
+  __shared__ uint64_t s_v[4][DCH];
+  __shared__ int64_t s_bk[4][WAVE];
+  __shared__ uint32_t s_last;
+  const int lane = lane_id();
+  const uint32_t wib = ufl(threadIdx.x / WAVE);
+  const uint32_t s = blockIdx.x * 4u + wib, s1 = a.n_kept;
+  const int fop = fap.op;
+  const int64_t I = a.interval;
+  const bool mine = s < s1;
+  int64_t acc = fap_neutral(fop);
+  // (scalar loads and a wave-uniform verdict, as ds_reg_body's prologue)
+  bool ok = mine && I > 0;
+  uint32_t W = 0;
+  uint64_t k1 = 0, k2 = 0;
+  DirSpan d = {};
+  RegSpan sp = {};
+  if (ok) {
+    dir_load(a, ncells, vlen, fap, s, d);
+    W = dir_fields(a, s, d);
+    ok = W != 0 && dir_key(a, d, W, k1, k2);
   }
   if (ok) {
-    const bool fail = W == 8 ? reg_piece<AGG, 8, false, false>(a, sp, r0, r0 + 1, ncells, s_v[wib], s_bk[wib], fop, s_part)
-                             : reg_piece<AGG, 4, false, false>(a, sp, r0, r0 + 1, ncells, s_v[wib], s_bk[wib], fop, s_part);
-    ok = !fail;
+    const uint32_t st = (uint32_t)(k2 >> 32);
+    sp.n = d.nc;
+    sp.t0 = (uint32_t)(k1 >> 32);
+    sp.step = st;
+    sp.kk = (uint32_t)((I + st - 1) / st);
+    sp.dkk.init(sp.kk);
+    const uint32_t nb = (sp.n + sp.kk - 1) / sp.kk;
+    // (assemble_finish's E capacity of the kept span: first >= start)
+    const uint32_t cap = min(sp.n, (uint32_t)((sp.n - 1) * st) / (uint32_t)I + 1u);
+    ok = nb <= WAVE && nb <= cap;
   }
+  if (ok)
+    ok = W == 8 ? reg_run<AGG, 8>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc)
+                : reg_run<AGG, 4>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc);
   if (mine && lane == 0) {  // the group's class: one key, no span outside it
     if (!ok) {
       if (!*(volatile uint32_t*)fap.broken) atomicOr(fap.broken, 1u);
     } else {
-      const unsigned long long k1 = ((unsigned long long)sp.t0 << 32) | sp.n;
-      const unsigned long long k2 = ((unsigned long long)sp.step << 32) | q0;
       volatile unsigned long long* kv = fap.key;
-      if (k1 < kv[0]) atomicMin(&fap.key[0], k1);
-      if (k1 > kv[1]) atomicMax(&fap.key[1], k1);
-      if (k2 < kv[2]) atomicMin(&fap.key[2], k2);
-      if (k2 > kv[3]) atomicMax(&fap.key[3], k2);
+      if (k1 < kv[0]) atomicMin(&fap.key[0], (unsigned long long)k1);
+      if (k1 > kv[1]) atomicMax(&fap.key[1], (unsigned long long)k1);
+      if (k2 < kv[2]) atomicMin(&fap.key[2], (unsigned long long)k2);
+      if (k2 > kv[3]) atomicMax(&fap.key[3], (unsigned long long)k2);
     }
   }
-  __syncthreads();  // the block's partial into its copy
-  if (threadIdx.x < WAVE) {
-    const int64_t v = s_part[threadIdx.x];
+  // the block's partial into its copy, then the block counts itself done
+  // (each wave's atomics acknowledged before the count)
+  s_bk[wib][lane] = acc;
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+  if (wib == 0) {
+    auto comb = [&](int64_t x, int64_t y) { return fop == 0 ? ladd(x, y) : (fop == 1 ? min(x, y) : max(x, y)); };
+    const int64_t v = comb(comb(s_bk[0][lane], s_bk[1][lane]), comb(s_bk[2][lane], s_bk[3][lane]));
     if (v != fap_neutral(fop)) {
-      unsigned long long* c = fap.copies + (uint64_t)(blockIdx.x % fap.ncopy) * WAVE + threadIdx.x;
+      unsigned long long* c = fap.copies + (uint64_t)(blockIdx.x % fap.ncopy) * WAVE + lane;
       if (fop == 0) atomicAdd(c, (unsigned long long)v);
       else if (fop == 1) atomicMin((long long*)c, (long long)v);
       else atomicMax((long long*)c, (long long)v);
     }
+    __builtin_amdgcn_s_waitcnt(0);
+    if (lane == 0) s_last = atomicAdd(done, 1u) == gridDim.x - 1 ? 1u : 0u;
   }
+  __syncthreads();
+  return s_last != 0;
 }
 
 #ifndef DS_WPE
