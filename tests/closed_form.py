@@ -136,7 +136,8 @@ def emitted(cells, start, interval, ds_agg):
 
 def spangroup(spans, start, end, agg, rate=False, interval=0, ds_agg=0):
     """spans: list of lists of KeyValue (well-formed, sorted, no Q1 seek).
-    Returns list of (ts, is_int, value) or raises ArithmeticError for NaN/Inf."""
+    Returns list of (ts, is_int, value) or raises ArithmeticError(index, points
+    before it) for NaN/Inf."""
     E = []
     for kvs in spans:
         cells = decode_cells(kvs)
@@ -160,7 +161,7 @@ def spangroup(spans, start, end, agg, rate=False, interval=0, ds_agg=0):
                 vals.append((float(y0) - yp) / float(x0 - xp))
             r = agg_double(agg, vals)
             if r != r or math.isinf(r):
-                raise ArithmeticError(len(out))
+                raise ArithmeticError(len(out), out)
             out.append((t, False, r))
             continue
         isf = False
@@ -184,7 +185,7 @@ def spangroup(spans, start, end, agg, rate=False, interval=0, ds_agg=0):
                     vals.append(float(y0) + (float(t - x0) * (float(y1) - float(y0))) / float(x1 - x0))
             r = agg_double(agg, vals)
             if r != r or math.isinf(r):
-                raise ArithmeticError(len(out))
+                raise ArithmeticError(len(out), out)
             out.append((t, False, r))
         else:
             vals = []
