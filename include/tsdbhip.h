@@ -118,6 +118,26 @@ typedef struct tsdbhip_ctx tsdbhip_ctx;
  * the compacted KeyValues of each span, rows sorted by time within a span.
  * qual_bytes / val_bytes hold exactly the KeyValue qualifier()/value() bytes
  * (big-endian, as stored in HBase); a row's qualifier offset must be even.
+ *
+ * Timestamps are 32 bits: the one deliberate departure from the reference.
+ * A row key holds 4 bytes of base time and a qualifier up to 4095 s on top of
+ * it, so a cell of the last hourly row (base 4294965600) can lie at or beyond
+ * 2^32. The reference carries such a timestamp as a long: alone in its group
+ * the cell is emitted when end_time admits it, and next to a second span the
+ * interpolation towards it throws (SpanGroup.java:719-727, "x1 out of
+ * range"). Here a span with a cell at or beyond 2^32 fails the call with
+ * TSDBHIP_E_INVALID_ARG (err_index 0, nothing emitted) while the spans are
+ * assembled, before any kernel runs on its cells and whatever the window.
+ * An end_time above 2^32 - 1 is therefore equivalent to 2^32 - 1, and a
+ * start_time above it keeps no span. Every cell of a row counts, whatever
+ * the order of the row's cells (a row with cells out of order that all lie
+ * below 2^32 is TSDBHIP_E_UNSORTED, as before).
+ *
+ * A span whose first cell is at timestamp 0 fails the call with
+ * TSDBHIP_E_OUT_OF_BOUNDS (err_index 0), as the reference does: Span.addRow
+ * starts from last_ts = 0, takes such a first row for one added out of order
+ * (Span.java:126) and throws from the log message's rows.get(rows.size() - 1)
+ * on the empty list, while TsdbQuery.findSpans scans the rows.
  */
 typedef struct tsdbhip_sg_desc {
   int64_t  start_time;      /* SpanGroup start (u32 held in int64)        */

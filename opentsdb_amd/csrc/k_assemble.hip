@@ -58,6 +58,25 @@ DEVI int64_t row_last_ts(const AssembleArgs& a, uint64_t r) {
   const uint32_t n = a.row_ncells[r];
   return (int64_t)a.row_base[r] + (load_qual(a.qual, a.row_qual_off[r] + 2ull * (n - 1)) >> 4);
 }
+// The last timestamp a span may hold (tsdbhip.h, "Timestamps are 32 bits"). Only
+// a row whose base is within a qualifier's 4095 s of it can hold a cell beyond
+// (row_near_top); such a row has every qualifier looked at, in whatever order
+// its cells come (row_past_top), so that no kernel after assembly ever narrows
+// a timestamp above TS_MAX to 32 bits. A span with such a cell, and a span whose
+// first cell is at timestamp 0, go to assemble_slow, which fails the call: the
+// thread-per-span walk scans a near-top row itself (a group that ends on 2^32 - 1
+// keeps its uniform proposal), the wave walks hand every near-top row on.
+constexpr int64_t TS_MAX = 0xFFFFFFFFll;
+DEVI bool row_near_top(int64_t base) { return base > TS_MAX - 4095; }
+DEVI bool row_past_top(const AssembleArgs& a, uint64_t r) {
+  const int64_t base = a.row_base[r];
+  if (!row_near_top(base)) return false;
+  const uint32_t n = a.row_ncells[r];
+  const uint64_t qo = a.row_qual_off[r];
+  for (uint32_t i = 0; i < n; i++)
+    if (base + (int64_t)(load_qual(a.qual, qo + 2ull * i) >> 4) > TS_MAX) return true;
+  return false;
+}
 DEVI uint32_t row_value_bytes(const AssembleArgs& a, uint64_t r) {
   // value bytes without the compacted meta byte (CompactionQueue.java:469-470)
   const uint32_t n = a.row_ncells[r], vl = a.row_val_len[r];
@@ -78,7 +97,13 @@ __device__ void assemble_slow(const AssembleArgs& a, uint32_t s, uint64_t r0, ui
     if (n == 0) { err_raise(a.err, 0, err_scan_order(a.row_base[r], a.span0 + s), -9 /*E_OUT_OF_BOUNDS*/); return; }
     const int64_t base = a.row_base[r];
     const int64_t first = row_first_ts(a, r), last = row_last_ts(a, r);
+    // a cell at or beyond 2^32, anywhere in the row: the call fails here, before any kernel
+    // narrows a timestamp to 32 bits
+    if (row_past_top(a, r)) { err_raise(a.err, 0, err_scan_order((uint32_t)base, a.span0 + s), -7 /*E_INVALID_ARG*/); return; }
     if (rs_base < 0) {
+      // Span.java:126-128 with no row yet: last_ts = 0 >= a first cell at timestamp 0, and the
+      // LOG.error message's rows.get(rows.size() - 1) throws from addRow
+      if (first == 0) { err_raise(a.err, 0, err_scan_order(0, a.span0 + s), -9 /*E_OUT_OF_BOUNDS*/); return; }
       a.row_ok[r] = 2; rs_base = base; rs_start = r; rs_vbytes = row_value_bytes(a, r); last_ts = last;
       continue;
     }
@@ -256,9 +281,9 @@ DEVI bool assemble_fast_one(const AssembleArgs& a, uint32_t s) {
       const uint32_t n = a.row_ncells[r];
       if (n == 0 || row_value_bytes(a, r) >= 32768u) { ok = false; break; }
       const int64_t base = a.row_base[r], first = row_first_ts(a, r), last = row_last_ts(a, r);
-      if (pb >= 0 && (base <= pb || first <= pl || last - pb < 4096)) { ok = false; break; }
+      if (row_past_top(a, r) || (pb >= 0 && (base <= pb || first <= pl || last - pb < 4096))) { ok = false; break; }
       if (r == r0) {
-        if (first < a.start) { ok = false; break; }  // Q1 seek inside the row
+        if (first < a.start || first == 0) { ok = false; break; }  // Q1 seek inside the row; the epoch
         first_ts = first;
       }
       pb = base;
@@ -333,7 +358,7 @@ DEVI bool assemble_walk(const AssembleArgs& a, uint32_t s, uint64_t r0, uint64_t
         vb = row_value_bytes(a, r);
       }
     }
-    if (ballot(valid && n == 0)) return false;  // (the slow walk reports it)
+    if (ballot(valid && (n == 0 || row_near_top(base)))) return false;  // (the slow walk reports it, or scans the row)
     const uint32_t nb = (uint32_t)min((uint64_t)WAVE, r1 - rb);
     uint32_t st = 0;  // this lane's row: 0 dropped, 1 merged, 2 starts a RowSeq
     for (uint32_t j = 0; j < nb; j++) {
@@ -362,7 +387,7 @@ DEVI bool assemble_walk(const AssembleArgs& a, uint32_t s, uint64_t r0, uint64_t
     }
     cell += readlane_u32(incl, 63);
   }
-  if (first_ts < a.start) return false;  // seek inside the first RowSeq (Q1): slow walk
+  if (first_ts < a.start || first_ts == 0) return false;  // seek inside the first RowSeq (Q1), the epoch: slow walk
   if (lane == 0) {
     a.sp_ncells[s] = cell;
     a.sp_first[s] = first_ts;
@@ -432,7 +457,7 @@ DEVI bool assemble_walk_pairs(const AssembleArgs& a, uint32_t s, uint64_t r0, ui
     if (lane == 0) { b1 = pb1; l1 = pl1; v1 = pv1; b2 = pb2; }
     if (lane == 1) b2 = pb1;
     const bool has1 = r > r0, has2 = r > r0 + 1;
-    const bool bad = valid && ((has1 && (base <= b1 || first <= l1)) || (has2 && last - b2 < 4096));
+    const bool bad = valid && (row_near_top(base) || (has1 && (base <= b1 || first <= l1)) || (has2 && last - b2 < 4096));
     if (ballot(bad)) return false;
     const bool c = valid && has1 && last - b1 < 4096;
     const uint64_t cm = ballot(c);
@@ -461,7 +486,7 @@ DEVI bool assemble_walk_pairs(const AssembleArgs& a, uint32_t s, uint64_t r0, ui
     pm1 = (ballot(m) >> t) & 1;
     last_all = pl1;
   }
-  if (first_ts < a.start) return false;  // seek inside the first RowSeq (Q1): slow walk
+  if (first_ts < a.start || first_ts == 0) return false;  // seek inside the first RowSeq (Q1), the epoch: slow walk
   if (lane == 0) {
     a.sp_ncells[s] = cell;
     a.sp_first[s] = first_ts;
@@ -495,9 +520,9 @@ DEVI void assemble_span_wave(const AssembleArgs& a, uint32_t s) {
       int64_t pb = (int64_t)shfl_up_u64((uint64_t)base, 1);
       int64_t pl = (int64_t)shfl_up_u64((uint64_t)last, 1);
       if (lane == 0) { pb = prev_base; pl = prev_last; }
-      bool bad = valid && (n == 0 || row_value_bytes(a, r) >= 32768u ||
+      bool bad = valid && (n == 0 || row_value_bytes(a, r) >= 32768u || row_near_top(base) ||
                            (pb >= 0 && (base <= pb || first <= pl || last - pb < 4096)));
-      if (valid && r == r0 && first < a.start) q1 = true;
+      if (valid && r == r0 && (first < a.start || first == 0)) q1 = true;  // (the epoch: the slow walk reports it)
       if (ballot(bad) != 0 || ballot(q1) != 0) { ok = false; break; }
       const uint32_t incl = wave_incl_scan_u32(n);
       if (valid) { a.row_ok[r] = 2; a.row_cell0[r] = cell + incl - n; }

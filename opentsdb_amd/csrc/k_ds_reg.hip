@@ -583,7 +583,8 @@ DEVI bool dir_key(const DecodeArgs& a, const DirSpan& d, uint32_t W, uint64_t& k
   const int64_t span = (int64_t)(d.nc - 1) * st, last = first + span;
   k1 = ((uint64_t)first << 32) | d.nc;
   k2 = ((uint64_t)st << 32) | q0;
-  return (q0 & 15u) == W - 1 && st >= 1 && first >= a.start && last <= a.end && last <= 0xFFFFFFFFll &&
+  // (first > 0: a span whose first cell is at timestamp 0 fails the call at assembly, k_assemble.hip)
+  return (q0 & 15u) == W - 1 && st >= 1 && first > 0 && first >= a.start && last <= a.end && last <= 0xFFFFFFFFll &&
          d0 + span <= 4095;
 }
 

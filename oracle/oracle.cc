@@ -356,7 +356,13 @@ struct Span {
     }
     std::unique_ptr<RowSeq> rowseq(new RowSeq());
     rowseq->setRow(row);
-    if (last_ts >= rowseq->timestamp(0)) return;  // LOG.error, dropped
+    if (last_ts >= rowseq->timestamp(0)) {
+      // :127-128: the LOG.error message evaluates rows.get(rows.size() - 1). With
+      // no row yet (last_ts = 0 and a first cell at timestamp 0) that is get(-1):
+      // addRow throws, while the scanner's rows are added, and the query fails.
+      if (rows.empty()) oob("ArrayIndexOutOfBounds: -1 (first cell of a span at timestamp 0)");
+      return;  // LOG.error, dropped
+    }
     rows.push_back(std::move(rowseq));
   }
   static int64_t lastTimestampInRow(const KeyValue& row) {  // :141-148

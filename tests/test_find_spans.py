@@ -22,6 +22,7 @@ import pytest
 
 from helpers import I, T0, U32MAX, assert_same
 from opentsdb_amd import _abi, compaction, core, packing, synth
+from time_domains import EDGE_BASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W3 = (3, 3, 3)
@@ -115,7 +116,36 @@ def scan_rows(rng, n_rows, w, hours, series=None, order="hbase"):
     return rows
 
 
+# EDGE_BASES: base times 0, either side of 2^31 (0x7FFF... and 0x8000...) and the last hourly row below
+# 2^32: the scan order and SpanCmp compare these key bytes unsigned, and row_base carries all 32 bits
+
+
+def edge_base_rows(w, order, seed=11, n_series=40):
+    """one scan whose rows sit at EDGE_BASES, some series missing from some hours"""
+    rng = np.random.default_rng(seed)
+    series = random_series(rng, n_series, w, max_tags=4)
+    m = metric_of(w)
+    keys = sorted(m + b.to_bytes(4, "big") + t for b in EDGE_BASES for t in series if rng.random() < 0.8)
+    assert [k[w[0]] >> 7 for k in keys] == sorted(k[w[0]] >> 7 for k in keys)  # (0x80.. and 0xFF.. bases last)
+    rows = [(k, i) for i, k in enumerate(keys)]
+    if order == "shuffled":
+        rows = [rows[i] for i in rng.permutation(len(rows))]
+    elif order == "reverse":
+        rows.sort(key=lambda r: (-int.from_bytes(r[0][w[0]:w[0] + 4], "big"), r[0]))
+    return rows
+
+
 # ===================================================================== CPU ====
+@pytest.mark.parametrize("w", WIDTHS)
+@pytest.mark.parametrize("order", ["hbase", "shuffled", "reverse"])
+def test_host_model_edge_base_times(w, order):
+    rows = edge_base_rows(w, order)
+    assert {int.from_bytes(k[w[0]:w[0] + 4], "big") for k, _ in rows} == set(EDGE_BASES)
+    got = core.find_spans(rows, metric_of(w), *w)
+    exp = brute_find_spans(rows, metric_of(w), w[0])
+    assert [(k, s.rows) for k, s in got.items()] == exp
+
+
 @pytest.mark.parametrize("w", WIDTHS)
 @pytest.mark.parametrize("order", ["hbase", "shuffled", "reverse"])
 def test_host_model_against_brute_force(w, order):
@@ -303,6 +333,20 @@ def test_parity_with_host_model(ctx, n, wi, hours):
     fs = check(ctx, parity_scan(n, wi, hours))
     assert fs.n_spans <= n and fs.n_rows == n
     assert ctx.timing().alg_bytes > parity_scan(n, wi, hours).key_bytes.nbytes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wi", [0, 1, 2])
+@pytest.mark.parametrize("order", ["hbase", "shuffled", "reverse"])
+def test_edge_base_times(ctx, wi, order):
+    """row keys whose 4-byte base time is 0, 2^31 -+ an hour and the last hour
+    below 2^32 in one scan: against core.find_spans, row_base included"""
+    w = WIDTHS[wi]
+    rows = edge_base_rows(w, order)
+    fs = check(ctx, Scan(rows, w, seed=wi))
+    assert set(fs.row_base.tolist()) == set(EDGE_BASES)
+    # a scan of more than one 1024-row tile
+    check(ctx, Scan(edge_base_rows(w, order, seed=12, n_series=700), w, seed=wi))
 
 
 @pytest.mark.gpu

@@ -20,6 +20,7 @@ import pytest
 
 from helpers import I, T0, U32MAX, assert_same
 from opentsdb_amd import _abi, core, packing
+from time_domains import EDGE_BASES  # (base times 0, either side of 2^31, the last hourly row below 2^32)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W3 = (3, 3, 3)
@@ -301,6 +302,27 @@ def test_wave_and_block_edges(ctx, n):
     keys = make_keys(n, 100 + n, [5, 6, 0x800000, 0x0201, 300], drop_every=7 if n > 7 else 0)
     check(ctx, keys, [uid(1)])
     check(ctx, keys, None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [97, 2 * GB_TILE + 5])
+def test_edge_base_times(ctx, n):
+    """keys that differ in their 4-byte base time only by these values: the
+    base time takes no part in SpanCmp, the grouping or the tags; against the
+    host plan"""
+    rng = np.random.default_rng(n)
+    keys = []
+    for i in range(n):
+        tags = [(1, int(rng.choice([5, 6, 0x800000, 0x0201]))), (2, int(rng.integers(0, 3))), (3, 7), (4, i)]
+        keys.append(key(9, EDGE_BASES[int(rng.integers(0, 4))], *(tags[1:] if i % 7 == 6 else tags)))
+    keys = sorted_keys(keys)
+    assert {int.from_bytes(k[3:7], "big") for k in keys} == set(EDGE_BASES)
+    kept = (rng.random(n) < 0.6).astype(np.uint8)
+    for gbs in ([uid(1)], [uid(1), uid(2)], None):
+        check(ctx, keys, gbs)
+        check(ctx, keys, gbs, kept.tolist())
+    gk, order, gss, _ = core.plan_groups_device(ctx, keys[::-1], [uid(1)])
+    assert (gk, order, gss) == core.plan_groups(keys[::-1], [uid(1)])
 
 
 @pytest.mark.gpu

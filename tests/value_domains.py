@@ -124,18 +124,19 @@ def _values(pool, s, S, n, kind, rng):
 
 
 class Group:
-    """series: [(kind, [(ts, value)])] in span order"""
+    """series: [(kind, [(ts, value)])] in span order; or (from_spans) the
+    spans' KeyValue rows as they are, with no series behind them"""
 
-    def __init__(self, pool, shape, series, **meta):
+    def __init__(self, pool, shape, series, spans=None, **meta):
         self.pool, self.shape, self.series, self.meta = pool, shape, series, meta
-        self.spans = [I(pts, minimal=False) if k == I8 else I(pts) if k == IM else F(pts, double=(k == F8))
-                      for k, pts in series]
+        self.spans = spans if spans is not None else [
+            I(pts, minimal=False) if k == I8 else I(pts) if k == IM else F(pts, double=(k == F8)) for k, pts in series]
         self.ss = packing.pack_spans(self.spans)
         flags = {kv.qualifier[i + 1] & 0xF for rows in self.spans for kv in rows for i in range(0, len(kv.qualifier), 2)}
         # one row a span and one cell type and width: what the uniform paths' class key asks for
         self.one_class = len(flags) == 1 and all(len(rows) == 1 for rows in self.spans)
-        self.is_float = any(k in (F4, F8) for k, _ in series)
-        self.n_spans = len(series)
+        self.is_float = any(f & 8 for f in flags) if series is None else any(k in (F4, F8) for k, _ in series)
+        self.n_spans = len(self.spans)
         self.key = (pool, shape) + tuple(sorted(meta.items(), key=str))
         self._abs = None
 
@@ -143,11 +144,16 @@ class Group:
         """the same group over |value|, longs as float64 cells (sums of them
         must not wrap): the aggregate over it bounds the sum of |terms| a
         double result is rounded against (assert_same's abs_scale)"""
+        assert self.series is not None, "a group made from rows has no |value| twin"
         if self._abs is None:
             self._abs = Group(self.pool, self.shape,
                               [(k if k == F4 else F8, [(t, abs(float(v))) for t, v in pts]) for k, pts in self.series],
                               abs_of=self.key)
         return self._abs
+
+    @classmethod
+    def from_spans(cls, pool, shape, spans, **meta):
+        return cls(pool, shape, None, spans=spans, **meta)
 
     def values(self, cell):
         """the spans' values at one cell (one_row)"""
