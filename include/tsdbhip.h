@@ -231,6 +231,9 @@ typedef struct tsdbhip_timing {
 #define TSDBHIP_PATH_GROUP_DIRECT_FALLBACK 128u  /* it was tried and the group
                                           did not stand: the call ran again
                                           from assembly                       */
+#define TSDBHIP_PATH_GROUP_DIRECT_LINES 256u  /* that launch (taken or fallen
+                                          back) read the values in whole lines
+                                          ("group_direct_load" lines_nt)      */
 
 /* ---- row compaction (CompactionQueue.compact) -------------------------- */
 /*
@@ -376,6 +379,11 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *                   of that launch streams as one run (wave g of G: spans g,
  *                   g + G, ...); "auto": 32 where the group still gives 16384
  *                   runs, else 16 or 8, else 1
+ *   "group_direct_load" "auto" | "rows" | "lines_nt"   how that launch loads a
+ *                   chunk's values: "rows", a lane its own 8 cells (lanes 64 B
+ *                   apart); "lines_nt", a wave instruction 1 KB contiguous with
+ *                   non-temporal loads, transposed through LDS; "auto":
+ *                   "lines_nt" (TSDBHIP_PATH_GROUP_DIRECT_LINES)
  *   "timing_detail" "on" | "off"   decode / grid event pairs in tsdbhip_timing
  *   "check_clean"   "on" | "off"   check the zero-on-entry invariants (stderr)
  *   "events"        "kernel" | "marker" | "none"   how tsdbhip_timing is measured:
@@ -663,6 +671,11 @@ int tsdbhip_desc_download(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* ddesc,
  * value bytes device-to-device, mode 2 is a flat grid-stride read of the
  * value bytes, mode 3 is mode 0 with two chunks in flight per wave and the
  * next span's metadata loaded ahead (width 8, single-row spans).
+ * On mode 3's geometry: mode 4 reads the values in whole lines (instruction i
+ * of a 512-cell chunk: lane l the 16 B at chunk + 1024 i + 16 l, 1 KB
+ * contiguous a wave instruction, where mode 3's lanes read 64 B apart),
+ * mode 5 is mode 3 with non-temporal loads, mode 6 mode 4 with them; mode 7
+ * is mode 2 with non-temporal loads. Any other mode: TSDBHIP_E_INVALID_ARG.
  * *ms = kernel time, *bytes = bytes moved.
  * `width` = value bytes per cell (4 or 8). Not part of the reference API:
  * it reports the achievable bandwidth beside the 8 TB/s peak. */

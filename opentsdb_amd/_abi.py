@@ -15,6 +15,7 @@ PATH_UNIFORM = 16  # every kept span proposed one class key at assembly: G from 
 PATH_UNIFORM_FALLBACK = 32  # the uniform aligned group did not stand: the general path ran the call
 PATH_GROUP_DIRECT = 64  # the aligned group of one-row spans ran straight from the descriptor (no assembly)
 PATH_GROUP_DIRECT_FALLBACK = 128  # it was tried and did not stand: the call ran again from assembly
+PATH_GROUP_DIRECT_LINES = 256  # that launch read the values in whole lines (group_direct_load lines_nt)
 
 OK = 0
 E_ILLEGAL_DATA = -1

@@ -71,6 +71,8 @@ struct Options {
                                // "off" (0), "on" (1: more than KC_MAX spans), "always" (2)
   int group_direct_run = 0;    // "group_direct_run": spans a wave of the direct group streams as one run:
                                // "auto" (0: ug_direct_run()), or 1, 2, 4, 8, 16, 32
+  int group_direct_load = -1;  // "group_direct_load": that launch's chunk loader (reg_run's LINES): "auto" (-1:
+                               // ug_direct_lines()), "rows" (0), "lines_nt" (1)
   bool timing_detail = false;  // "timing_detail": decode / grid event pairs (tsdbhip_timing)
   bool check_clean = false;    // "check_clean": verify the zero-on-entry invariants (stderr)
   int events = 0;              // "events": timing events on kernel launches (0), marker packets (1), none (2)
@@ -106,6 +108,7 @@ struct Slot {
   int8_t ev_alias[10] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // "kernel" events: a start no kernel carried reads as this one (-1: none)
   bool time_reduce = false;  // the dominant kernel is k_reduce (direct path)
   uint32_t hot_kernel = 0;
+  uint32_t gd_load_path = 0;  // TSDBHIP_PATH_GROUP_DIRECT_LINES if the call's direct launch used the whole-line loader
   tsdbhip_timing timing = {};
   Xchg* x = nullptr;  // the exchange of a sharded call (its rank / nranks)
   Options opt;        // the context's options, copied at the lease
@@ -579,6 +582,12 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
   else if (n == "group_direct_run") {
     ok = v == "auto" || v == "1" || v == "2" || v == "4" || v == "8" || v == "16" || v == "32";
     o.group_direct_run = v == "auto" ? 0 : std::atoi(v.c_str());
+  }
+  else if (n == "group_direct_load") {
+    static const char* names[] = {"auto", "rows", "lines_nt"};
+    ok = false;
+    for (int i = 0; i < 3; i++)
+      if (v == names[i]) { o.group_direct_load = i - 1; ok = true; }
   }
   else if (n == "timing_detail") ok = on_off(o.timing_detail);
   else if (n == "check_clean") ok = on_off(o.check_clean);
@@ -1882,8 +1891,9 @@ DEVI void ug_fap_tail_direct(const FapArgs& fap, const UgTail& t) {
   small_snap(sm, t.snap, s_ok ? t.init : nullptr, t.seq);
 }
 // (DIRECT: the launch with no assembly before it, ds_reg_direct_body; a
-// template argument of its own, so the other instantiations carry none of it)
-template <int AGG, bool SPEC, bool DIRECT = false>
+// template argument of its own, so the other instantiations carry none of it;
+// LINES: its chunk loader, reg_run)
+template <int AGG, bool SPEC, bool DIRECT = false, bool LINES = false>
 #ifndef UG_LDS_CAP
 #define UG_LDS_CAP 40960u  // (build knob) LDS a k_ug_ds_reg block claims: 40 KB = 4 blocks a CU
 #endif
@@ -1906,7 +1916,7 @@ k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
   }
   if constexpr (DIRECT) {
     // (the body counts its block done itself: one barrier pair per 4 runs)
-    if (ds_reg_direct_body<AGG>(a, ncells, vlen, fap, &t.sm->ug_done)) ug_fap_tail_direct(fap, t);
+    if (ds_reg_direct_body<AGG, LINES>(a, ncells, vlen, fap, &t.sm->ug_done)) ug_fap_tail_direct(fap, t);
     return;
   }
   ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
@@ -2100,6 +2110,9 @@ static uint32_t ug_direct_run(int opt, uint32_t n_kept) {
   while (r > 1 && n_kept / r < UG_RUN_FILL) r >>= 1;
   return r >= 8 ? r : 1u;
 }
+// ... and its chunk loader (reg_run's LINES), "group_direct_load": "auto" is the whole-line loader, which
+// measured faster at every group size tried
+static bool ug_direct_lines(int opt) { return opt != 0; }
 
 // the aligned group (k_ug_ds_reg; sharded: one collective group and
 // k_fap_finish_end); RC_UG_FALLBACK when the group did not stand
@@ -2201,7 +2214,8 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
                    ? (unsigned)at.sharedSizeBytes
                    : 21000u;
       }();
-      // (the direct instantiation's own static LDS: the block claims exactly UG_LDS_CAP)
+      // (the direct instantiation's own static LDS: the block claims exactly UG_LDS_CAP; the
+      // loaders share it, the whole-line one transposes in place)
       static const unsigned stat_lds_direct = [] {
         hipFuncAttributes at = {};
         return hipFuncGetAttributes(&at, (const void*)k_ug_ds_reg<A, false, true>) == hipSuccess
@@ -2211,10 +2225,16 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
       const unsigned pad = stat_lds < UG_LDS_CAP ? UG_LDS_CAP - stat_lds : 0u;
       const unsigned pad_direct = stat_lds_direct < UG_LDS_CAP ? UG_LDS_CAP - stat_lds_direct : 0u;
       EV_START(ctx, 8);
-      if (u.direct)
-        LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ug_ds_reg<A, false, true>), dim3(rblocks), dim3(256), pad_direct, st, u.da, gr,
-                    u.row_ncells, u.row_val_len, fa, t);
-      else if (u.spec)
+      if (u.direct) {
+        const bool lines = ug_direct_lines(ctx->opt.group_direct_load);
+        if (lines) ctx->gd_load_path = TSDBHIP_PATH_GROUP_DIRECT_LINES;
+        auto direct = [&](auto k) {
+          LAUNCH_STOP(EV_STOP_K(ctx, 9), k, dim3(rblocks), dim3(256), pad_direct, st, u.da, gr, u.row_ncells,
+                      u.row_val_len, fa, t);
+        };
+        if (lines) direct(k_ug_ds_reg<A, false, true, true>);
+        else direct(k_ug_ds_reg<A, false, true>);
+      } else if (u.spec)
         LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ug_ds_reg<A, true>), dim3(rblocks), dim3(256), pad, st, u.da, gr,
                     u.row_ncells, u.row_val_len, fa, t);
       else
@@ -3968,6 +3988,7 @@ static int spangroup_run(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_out* ou
   } reuse{ctx};
   ctx->h2d_bytes = 0;
   ctx->reuse_inputs = false;
+  ctx->gd_load_path = 0;
   uint32_t paths = 0;
   int rc = 0;
   for (SgAttempt a = SG_FIRST; a != SG_DONE;) {
@@ -3993,7 +4014,7 @@ static int spangroup_run(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_out* ou
     ctx->reuse_inputs = true;
     a = next;
   }
-  ctx->timing.paths |= paths;
+  ctx->timing.paths |= paths | ctx->gd_load_path;  // (the loader of a direct launch, taken or fallen back)
   ctx->timing.h2d_bytes = ctx->h2d_bytes;
   return rc;
 }
@@ -4493,8 +4514,9 @@ static int compact_rows(Slot* ctx, const tsdbhip_rows_desc* d, tsdbhip_rows_out*
 
 // ------------------------------------------------------ bandwidth probe ---
 // mode 0: streaming read of a device desc's row bytes with k_ds_spans'
-// geometry; mode 1: device-to-device copy of its value bytes. Returns the
-// kernel time (HIP events) and the bytes it moved.
+// geometry; mode 1: device-to-device copy of its value bytes; modes 2-7: see
+// include/tsdbhip.h; any other mode is E_INVALID_ARG. Returns the kernel time
+// (HIP events) and the bytes it moved.
 extern "C" int tsdbhip_bw_probe(tsdbhip_ctx* c, const tsdbhip_sg_desc* d, int32_t mode, uint32_t width,
                                 float* ms, uint64_t* bytes) {
   if (!c || !d || !ms || !bytes || !(d->flags & TSDBHIP_DESC_DEVICE) || (width != 4 && width != 8))
@@ -4503,16 +4525,32 @@ extern "C" int tsdbhip_bw_probe(tsdbhip_ctx* c, const tsdbhip_sg_desc* d, int32_
     Lease L(plain_of(c));
     Slot* ctx = L.s;
     hipStream_t st = ctx->stream;
+    if (mode < 0 || mode > 7) return TSDBHIP_E_INVALID_ARG;
     uint32_t* sink = scratch<uint32_t>(ctx, "probe_sink", 1);
     HIPCHK(hipEventRecord(ctx->ev[0], st));
-    if (mode == 0) {
+    if (mode >= 4 && mode <= 6) {
+      // mode 3's geometry: 4 whole-line value loads, 5 its loads non-temporal, 6 both (8-byte cells)
+      auto go = [&](auto k) {
+        LAUNCH(k, dim3(grid_for(d->n_spans, 4, 1u << 20)), dim3(256), 0, st, d->span_row_start, d->row_ncells,
+               d->row_qual_off, d->row_val_off, d->qual_bytes, d->val_bytes, d->n_spans, sink);
+      };
+      if (mode == 4) go(k_probe_read2v<true, false>);
+      else if (mode == 5) go(k_probe_read2v<false, true>);
+      else go(k_probe_read2v<true, true>);
+      *bytes = d->qual_nbytes + d->val_nbytes;
+    } else if (mode == 7) {  // mode 2 with non-temporal loads
+      const uint64_t n16 = d->val_nbytes / 16;
+      LAUNCH(k_probe_flat<true>, dim3(grid_for(n16, 1024, 1u << 16)), dim3(256), 0, st, (const uint4*)d->val_bytes,
+             n16, sink);
+      *bytes = n16 * 16;
+    } else if (mode == 0) {
       LAUNCH(k_probe_read, dim3(grid_for(d->n_spans, 4, 1u << 20)), dim3(256), 0, st, d->span_row_start,
                          d->row_ncells, d->row_qual_off, d->row_val_off, d->qual_bytes, d->val_bytes, d->n_spans,
                          width, sink);
       *bytes = d->qual_nbytes + d->val_nbytes;
     } else if (mode == 2) {
       const uint64_t n16 = d->val_nbytes / 16;
-      LAUNCH(k_probe_flat, dim3(grid_for(n16, 1024, 1u << 16)), dim3(256), 0, st,
+      LAUNCH(k_probe_flat<false>, dim3(grid_for(n16, 1024, 1u << 16)), dim3(256), 0, st,
                          (const uint4*)d->val_bytes, n16, sink);
       *bytes = n16 * 16;
     } else if (mode == 3) {

@@ -169,6 +169,19 @@ DEVI void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// A 16-B global load at the default cache policy or non-temporal (NT: the
+// `nt` bit of global_load_dwordx4, a once-read stream; the builtin takes an
+// ext_vector_type pointer, not uint4).
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+template <bool NT>
+DEVI uint4 ld16(const void* p) {
+  if (NT) {
+    const u32x4_t v = __builtin_nontemporal_load((const u32x4_t*)p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+  }
+  return *(const uint4*)p;
+}
+
 // Host-visible publish of a small device state (a call's host round trip
 // without a copy and a stream sync): one wave copies nwords 8-byte words of
 // src (device-coherent loads) into mapped pinned host memory, fences at

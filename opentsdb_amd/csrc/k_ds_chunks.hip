@@ -63,7 +63,13 @@ struct RawW {
 // Branch-free chunk load of 8 consecutive cells per lane; c is clamped into
 // the row by the caller. Reads up to 7 cells past the row end (inside the
 // buffers' 64-byte slack). Lanes read 16 B of qualifiers and 8W bytes of
-// values each (plain loads: non-temporal ones measured 15 % slower).
+// values each. Plain loads: on this geometry — lanes 64 B apart, so each of
+// the four value instructions touches all 32 lines of a 4-KB range and a line
+// is asked for four times — non-temporal ones lose, the line being dropped
+// between the instructions that complete it (the probe on C3*'s buffers 4.10
+// against 6.33 TB/s, the direct aligned group 8.63 against 5.79 ms a step;
+// an earlier measurement on k_ds_spans gave -15 %). On whole-line loads (1 KB
+// contiguous a wave instruction) they gain instead: DESIGN.md §5.
 template <int W>
 DEVI void load_raw(const DecodeArgs& a, uint64_t qoff, uint64_t voff, uint32_t c, RawW<W>& x) {
   x.q = *(const uint4*)(a.qual + qoff + 2ull * c);

@@ -617,11 +617,26 @@ DEVI int64_t ldiv64_4096(int64_t a, uint32_t n) {
 // whole span, bucket b at BK[b]), carried on across the spans of the run.
 // `acc` takes the spans' buckets (lane b: bucket b; fop: 0 wrapping add,
 // 1 min, 2 max). Returns false when a span of the run is not a member.
-template <int AGG, int W>
+//
+// LINES, the chunk loader ("group_direct_load"): false `rows`, load_raw — a
+// lane its 8 cells, so a value load instruction touches a 4-KB range at 16 B
+// in every 64 and four instructions complete each line; true `lines_nt` —
+// instruction i of a chunk loads the 16 B at chunk + 1024 i + 16 lane, 1 KB
+// contiguous (8 whole lines) a wave instruction, non-temporal (each line is
+// asked for once), into the same registers, and `stage` transposes them
+// through L_v into load_raw's layout. The qualifier load, 1 KB contiguous
+// already, keeps the default policy: non-temporal it measured slower and
+// fetched more. A lane whose piece starts at or past the row's
+// end reads the piece that holds the row's last cell instead (at most 16 - W
+// bytes past the row's values; load_raw: 7 cells), and an instruction whose
+// whole range is past the end is skipped, a scalar branch (the 16-cell last
+// chunk of a 3600-cell row would fetch the row's last line three times more).
+template <int AGG, int W, bool LINES = false>
 DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap,
                   const RegSpan& sp, uint32_t base, uint64_t k1, uint64_t k2, const DirSpan& d0, uint32_t s,
                   uint32_t s1, uint64_t* L_v, int64_t* BK, int fop, int64_t& acc) {
   constexpr bool PREFIX = AGG == 0 || AGG == 3;  // wrapping sums: prefix differences
+  constexpr uint32_t NV = 2 * W / 4, CP = 16 / W;  // a lane's 16-B value pieces a chunk, cells a piece
   const int lane = lane_id();
   const uint32_t fl = (uint32_t)(W - 1);
   const uint32_t n = sp.n, kk = sp.kk;
@@ -674,19 +689,56 @@ DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* v
     return q;  // (done: the same chunk again — its load stays in the row)
   };
   RawW<W> A, B;
+  if (LINES) {  // (a skipped load leaves its registers as they are: cells past n, masked at `stage`)
+    A = RawW<W>{};
+    B = RawW<W>{};
+  }
   auto issue = [&](const Pos& p, RawW<W>& x) {
     const uint32_t c = p.c0 + 8u * lane;
     __builtin_amdgcn_s_setprio(2);
-    load_raw<W>(a, p.qo, p.vo, c < n ? c : (n - 1) & ~7u, x);
+    if (!LINES) {
+      load_raw<W>(a, p.qo, p.vo, c < n ? c : (n - 1) & ~7u, x);
+    } else {
+      x.q = *(const uint4*)(a.qual + p.qo + 2ull * (c < n ? c : (n - 1) & ~7u));
+      const uint8_t* pv = a.val + p.vo;
+      const uint32_t c0 = ufl(p.c0);
+#pragma unroll
+      for (uint32_t i = 0; i < NV; i++) {
+        const uint32_t ci = c0 + 64u * CP * i;  // the instruction's first cell: wave-uniform, a scalar branch
+        if (i > 0 && ci >= n) continue;
+        const uint32_t cv = ci + CP * (uint32_t)lane;
+        x.v[i] = ld16<true>(pv + (uint64_t)W * (cv < n ? cv : (n - 1) & ~(CP - 1u)));
+      }
+    }
     __builtin_amdgcn_s_setprio(0);
   };
   bool bad = false;
   int64_t carry = 0;    // the open bucket's value over its cells in earlier chunks
   uint32_t bcur = 0, ph = 0;  // bucket of the next chunk's first cell and that cell's place in it
   // decode + qualifier check + LDS staging of one chunk (FULL: 512 cells)
-  auto stage = [&](auto full, const RawW<W>& cur, uint32_t nv, uint32_t cs) {
+  auto stage = [&](auto full, const RawW<W>& ld, uint32_t nv, uint32_t cs) {
     constexpr bool FULL = decltype(full)::value;
     const uint32_t nmine = FULL ? 8u : (nv > 8u * lane ? min(8u, nv - 8u * lane) : 0u);
+    // (LINES) the pieces into L_v in cell order (linear 16-B writes at 1024 i +
+    // 16 lane), then each lane's own 8 cells back: the same segment of L_v its
+    // prefixes go to below (W 4: the first half of it, hence the second sync),
+    // the previous step's readers being behind that step's closing sync
+    RawW<W> tr;
+    if (LINES) {
+      // (W 8: lane L's piece p sits at slot (p + (L >> 2)) & 3 of its 64 bytes, so the 8 lanes of a
+      // ds_read_b128 group, 64 B apart, hit 8 distinct 16-B bank quads, and so do the writers')
+      uint4* Lq = (uint4*)L_v;
+      const uint32_t l = (uint32_t)lane;
+      const uint32_t wq = W == 8 ? ((l & ~3u) | ((l + (l >> 4)) & 3u)) : l;
+#pragma unroll
+      for (uint32_t i = 0; i < NV; i++) Lq[64u * i + wq] = ld.v[i];
+      wave_lds_sync();
+      tr.q = ld.q;
+#pragma unroll
+      for (uint32_t i = 0; i < NV; i++) tr.v[i] = Lq[NV * l + (W == 8 ? ((i + (l >> 2)) & 3u) : i)];
+      if (W == 4) wave_lds_sync();
+    }
+    const RawW<W>& cur = LINES ? tr : ld;
     {  // (t0 + c step - base) << 4 | flags, two cells per dword
       const uint32_t dd = sp.t0 + (cs + 8u * lane) * sp.step - base;
       uint32_t e = ((dd << 4) | fl) * 0x00010001u + (sp.step << 20);
@@ -790,7 +842,7 @@ DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* v
 }
 
 // Returns true in every thread of the launch's last block to finish.
-template <int AGG>
+template <int AGG, bool LINES = false>
 DEVI bool ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap,
                              uint32_t* done) {
   __shared__ uint64_t s_v[4][DCH];
@@ -827,8 +879,8 @@ DEVI bool ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const 
     ok = nb <= WAVE && nb <= cap;
   }
   if (ok)
-    ok = W == 8 ? reg_run<AGG, 8>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc)
-                : reg_run<AGG, 4>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc);
+    ok = W == 8 ? reg_run<AGG, 8, LINES>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc)
+                : reg_run<AGG, 4, LINES>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc);
   if (mine && lane == 0) {  // the group's class: one key, no span outside it
     if (!ok) {
       if (!*(volatile uint32_t*)fap.broken) atomicOr(fap.broken, 1u);

@@ -646,15 +646,18 @@ __global__ void __launch_bounds__(256) k_probe_copy(const uint4* src, uint4* dst
 
 // Flat streaming read of [p, p + n16*16): 4 x 16 B per lane in flight per
 // iteration, grid-stride (the pure-read ceiling of the box).
+// (NT: non-temporal loads, ld16)
+template <bool NT>
 __global__ void __launch_bounds__(256) k_probe_flat(const uint4* p, uint64_t n16, uint32_t* sink) {
   uint32_t acc = 0;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + 3 * stride < n16; i += 4 * stride) {
-    const uint4 a = p[i], b = p[i + stride], c = p[i + 2 * stride], d = p[i + 3 * stride];
+    const uint4 a = ld16<NT>(p + i), b = ld16<NT>(p + i + stride), c = ld16<NT>(p + i + 2 * stride),
+                d = ld16<NT>(p + i + 3 * stride);
     acc ^= a.x ^ b.y ^ c.z ^ d.w;
   }
-  for (; i < n16; i += stride) acc ^= p[i].x;
+  for (; i < n16; i += stride) acc ^= ld16<NT>(p + i).x;
   if (acc == 0x9e3779b9u) sink[0] = acc;
 }
 
@@ -698,6 +701,63 @@ __global__ void __launch_bounds__(256) k_probe_read2(const uint64_t* span_row_st
       }
       acc ^= a.x ^ a.y ^ a.z ^ a.w ^ a2.x ^ a2.w;
       for (int i = 0; i < 4; i++) acc ^= b[i].x ^ b[i].w ^ b2[i].y ^ b2[i].z;
+    }
+    nc = ncn;
+    qo = qn;
+    vo = vn;
+  }
+  if (acc == 0x9e3779b9u) sink[0] = acc;
+}
+
+// k_probe_read2's geometry with the value loads and the cache policy as
+// template arguments. LINES: instruction i of a 512-cell chunk has lane l read
+// the 16 B at chunk + 1024 i + 16 l, so a wave instruction covers 1 KB
+// contiguous (8 whole lines) where k_probe_read2's lanes read 64 B apart (32
+// lines at a quarter each, four instructions completing a line). NT: the
+// value and the qualifier loads non-temporal. (8-byte cells; a piece whose
+// first cell is inside the row is read whole: at most 8 B past the row's
+// values, k_probe_read2 reads up to 56.)
+template <bool LINES, bool NT>
+__global__ void __launch_bounds__(256) k_probe_read2v(const uint64_t* span_row_start, const uint32_t* ncells,
+                                                      const uint64_t* qoff, const uint64_t* voff,
+                                                      const uint8_t* qual, const uint8_t* val, uint32_t n_spans,
+                                                      uint32_t* sink) {
+  const int lane = lane_id();
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  const uint32_t nwaves = gridDim.x * blockDim.x / WAVE;
+  uint32_t acc = 0;
+  uint32_t s = wave;
+  if (s >= n_spans) return;
+  uint64_t r = span_row_start[s];
+  uint32_t nc = ncells[r];
+  uint64_t qo = qoff[r], vo = voff[r];
+  for (; s < n_spans; s += nwaves) {
+    const uint32_t sn = s + nwaves;
+    uint64_t rn = 0, qn = 0, vn = 0;
+    uint32_t ncn = 0;
+    if (sn < n_spans) {
+      rn = span_row_start[sn];
+      ncn = ncells[rn];
+      qn = qoff[rn];
+      vn = voff[rn];
+    }
+    const uint8_t* q = qual + qo;
+    const uint8_t* v = val + vo;
+    for (uint32_t c0 = 0; c0 < nc; c0 += 1024) {
+      uint4 a[2] = {}, b[2][4] = {};
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const uint32_t ch = c0 + 512u * h, c = ch + 8u * lane;
+        if (c < nc) a[h] = ld16<NT>(q + 2ull * c);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const uint32_t cv = LINES ? ch + 128u * i + 2u * lane : c;
+          const uint64_t o = LINES ? 8ull * ch + 1024ull * i + 16ull * lane : 8ull * c + 16ull * i;
+          if (cv < nc) b[h][i] = ld16<NT>(v + o);
+        }
+      }
+      acc ^= a[0].x ^ a[0].y ^ a[0].z ^ a[0].w ^ a[1].x ^ a[1].w;
+      for (int i = 0; i < 4; i++) acc ^= b[0][i].x ^ b[0][i].w ^ b[1][i].y ^ b[1][i].z;
     }
     nc = ncn;
     qo = qn;
