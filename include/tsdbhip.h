@@ -119,6 +119,31 @@ typedef struct tsdbhip_ctx tsdbhip_ctx;
  * qual_bytes / val_bytes hold exactly the KeyValue qualifier()/value() bytes
  * (big-endian, as stored in HBase); a row's qualifier offset must be even.
  *
+ * Layout (tests/layouts.py, tests/test_layouts.py: every kernel path on each
+ * of these). Rows may lie anywhere inside qual_bytes / val_bytes, in any order
+ * (offsets need not grow with the row index: tsdbhip_desc_gather's output,
+ * a shuffled or reversed buffer) and at any value offset; qualifier offsets
+ * must be even; rows must not share bytes. Bytes outside rows (a lead, gaps,
+ * the tail; tsdbhip_rows_out's "bytes between rows") are read by the wide
+ * loads and never interpreted: results do not depend on them. What keeps a
+ * row on the streaming paths is its alignment, 8 B for its qualifier offset
+ * and 16 B for its value offset (packing.pack_spans' layout); the lockstep /
+ * uniform paths without downsampling (k_lockstep, k_ug_dev) take any even
+ * qualifier offset with a value offset that is a multiple of the cell width.
+ * Any other row takes the general path at its cost, and a group that holds
+ * one falls back as a whole from the aligned group and its direct form
+ * (tsdbhip_timing.paths: TSDBHIP_PATH_ALIGNED_RERUN, _UNIFORM_FALLBACK,
+ * _GROUP_DIRECT_FALLBACK): tsdbhip_compact_rows' placement (value offsets at
+ * every residue) is such a layout.
+ * With TSDBHIP_DESC_DEVICE the allocations behind qual_bytes and val_bytes
+ * must be readable for 64 bytes past qual_nbytes / val_nbytes (their
+ * contents are never interpreted): the loaders read whole groups past a
+ * row's end, at most k_ds_chunks.hip load_raw's 7 cells (56 B of values, 14 B
+ * of qualifiers; k_decode_fast.hip load_chunk 3 cells; k_lockstep.hip and
+ * k_ds_reg.hip reg_run a 16-B group, 14 B), and dev_common.h load_be_bytes
+ * 12 B from the dword that holds a value's first byte. A host descriptor
+ * needs no such slack: its buffers are copied with it added.
+ *
  * Timestamps are 32 bits: the one deliberate departure from the reference.
  * A row key holds 4 bytes of base time and a qualifier up to 4095 s on top of
  * it, so a cell of the last hourly row (base 4294965600) can lie at or beyond
