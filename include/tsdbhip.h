@@ -400,10 +400,16 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *                   an aligned-group query): "on" for groups of more than 4096
  *                   spans, "always" for any group; a group that is not one runs
  *                   again from assembly (TSDBHIP_PATH_GROUP_DIRECT*)
- *   "group_direct_run" "auto" | "1" | "2" | "4" | "8" | "16" | "32"   spans a wave
- *                   of that launch streams as one run (wave g of G: spans g,
- *                   g + G, ...); "auto": 32 where the group still gives 16384
- *                   runs, else 16 or 8, else 1
+ *   "group_direct_run" "auto" | "fill" | "1" | "2" | "4" | ... | "256"   spans a
+ *                   wave of that launch streams as one run (wave g of G: spans
+ *                   g, g + G, ...): a number r gives ceil(n / 4 r) blocks;
+ *                   "fill" gives min(ceil(n / 4), resident blocks), one
+ *                   generation of blocks whose waves share the whole group;
+ *                   "auto": "fill"
+ *   "group_direct_blocks" "auto" | a positive count   what "fill" takes for the
+ *                   resident blocks: "auto" the device's (CUs x the blocks a CU
+ *                   holds of that kernel); a count lets a small group reach
+ *                   long runs (tests)
  *   "group_direct_load" "auto" | "rows" | "lines_nt"   how that launch loads a
  *                   chunk's values: "rows", a lane its own 8 cells (lanes 64 B
  *                   apart); "lines_nt", a wave instruction 1 KB contiguous with

@@ -70,7 +70,10 @@ struct Options {
   int group_direct = 1;        // "group_direct": the aligned group of one-row spans launched with no assembly:
                                // "off" (0), "on" (1: more than KC_MAX spans), "always" (2)
   int group_direct_run = 0;    // "group_direct_run": spans a wave of the direct group streams as one run:
-                               // "auto" (0: ug_direct_run()), or 1, 2, 4, 8, 16, 32
+                               // "auto" (0: "fill"), 1, 2, 4, ..., 256, or "fill" (-1: one resident generation
+                               // of blocks, each wave a share of the whole group; ug_direct_grid())
+  int group_direct_blocks = 0; // "group_direct_blocks": the blocks "fill" takes for resident: "auto" (0: the
+                               // device's), or a count (small test groups reach long runs with it)
   int group_direct_load = -1;  // "group_direct_load": that launch's chunk loader (reg_run's LINES): "auto" (-1:
                                // ug_direct_lines()), "rows" (0), "lines_nt" (1)
   bool timing_detail = false;  // "timing_detail": decode / grid event pairs (tsdbhip_timing)
@@ -580,8 +583,14 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
     o.group_direct = v == "off" ? 0 : (v == "on" ? 1 : 2);
   }
   else if (n == "group_direct_run") {
-    ok = v == "auto" || v == "1" || v == "2" || v == "4" || v == "8" || v == "16" || v == "32";
-    o.group_direct_run = v == "auto" ? 0 : std::atoi(v.c_str());
+    ok = v == "auto" || v == "fill" || v == "1" || v == "2" || v == "4" || v == "8" || v == "16" || v == "32" ||
+         v == "64" || v == "128" || v == "256";
+    o.group_direct_run = v == "auto" ? 0 : (v == "fill" ? -1 : std::atoi(v.c_str()));
+  }
+  else if (n == "group_direct_blocks") {
+    const long b = v == "auto" ? 0 : std::strtol(v.c_str(), nullptr, 10);
+    ok = v == "auto" || (b > 0 && b <= (1 << 20) && v.find_first_not_of("0123456789") == std::string::npos);
+    o.group_direct_blocks = (int)b;
   }
   else if (n == "group_direct_load") {
     static const char* names[] = {"auto", "rows", "lines_nt"};
@@ -2094,25 +2103,69 @@ static uint32_t ug_e_pieces(uint32_t t0, uint32_t step, uint32_t n, uint32_t kk,
   return 1;
 }
 
-// Spans a wave of the direct group (ds_reg_direct_body) takes as one run: the
-// grid is sized for it, ceil(n_kept / 4 run) blocks, and wave g takes every
-// span g + k * (4 blocks). "auto": UG_RUN spans (C3*, one box: 1 / 4 / 8 / 16 /
-// 32 spans 6.29 / 6.33 / 6.22 / 6.07 / 5.96 ms a step) where that
-// still leaves UG_RUN_FILL runs — 4 times the 4096 waves resident on 256 CUs
-// at 4 blocks each, so that the launch's last, partly filled round stays a
-// small part of it — else the largest power of two below it that does; runs
-// of 2 and 4 measured no faster than none, so below 8 a wave takes one span
-// (a small group: as many waves as it has spans).
-constexpr uint32_t UG_RUN = 32, UG_RUN_FILL = 16384;
-static uint32_t ug_direct_run(int opt, uint32_t n_kept) {
-  if (opt > 0) return (uint32_t)opt;
-  uint32_t r = UG_RUN;
-  while (r > 1 && n_kept / r < UG_RUN_FILL) r >>= 1;
-  return r >= 8 ? r : 1u;
+// The grid of the direct group (ds_reg_direct_body): wave g of the launch's G = 4 blocks waves takes the
+// spans g, g + G, ... as one run, so the grid decides the run length. "group_direct_run":
+//   a number r: ceil(n_kept / 4 r) blocks, r spans a wave;
+//   "fill": one resident generation, min(ceil(n_kept / 4), resident blocks) — no block waits for another
+//     to leave, there is no last, partly filled round, and a shard of any size streams runs as long as
+//     the whole group's (resident blocks: the device's CUs x the blocks a CU holds of the instantiation
+//     launched with its padded LDS, or "group_direct_blocks"); a group of up to 4 x resident spans is a
+//     span a wave, as before;
+//   "auto": "fill". Same box, parent (32 spans a wave where that left 16384 runs, else 16, 8 or 1) and
+//     "fill" alternating, 6 rounds, medians of ms a step: 1M spans 5.803 -> 5.548, 500,000
+//     2.960 -> 2.800, 250,000 1.525 -> 1.408 and 1.496 -> 1.401, 125,000 0.804 -> 0.734, 16,000 0.154 ->
+//     0.123, every run below every parent run at each size. Runs of 64 / 128 / 256 at 1M: 5.757 / 5.737 /
+//     5.981 against 5.701 for "fill" beside them (256 leaves 977 blocks for 1024 places).
+static uint32_t ug_direct_grid(int opt, uint32_t n_kept, uint32_t resident) {
+  const uint64_t n = n_kept;
+  if (opt <= 0) return (uint32_t)std::min<uint64_t>((n + 3) / 4, std::max(resident, 1u));
+  return (uint32_t)((n + 4 * (uint64_t)opt - 1) / (4 * (uint64_t)opt));
 }
 // ... and its chunk loader (reg_run's LINES), "group_direct_load": "auto" is the whole-line loader, which
 // measured faster at every group size tried
 static bool ug_direct_lines(int opt) { return opt != 0; }
+// ... and the blocks of that launch resident at one time (cached: an occupancy query an instantiation, an
+// attribute query a device)
+template <int A, bool LINES>
+static uint32_t ug_direct_blocks_per_cu() {
+  static const uint32_t bpc = [] {
+    const void* k = (const void*)k_ug_ds_reg<A, false, true, LINES>;
+    hipFuncAttributes at = {};
+    const unsigned stat = hipFuncGetAttributes(&at, k) == hipSuccess ? (unsigned)at.sharedSizeBytes : 21000u;
+    const unsigned pad = stat < UG_LDS_CAP ? UG_LDS_CAP - stat : 0u;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 256, pad) != hipSuccess || nb < 1) nb = 1;
+    return (uint32_t)nb;
+  }();
+  return bpc;
+}
+static uint32_t ug_direct_resident(Slot* ctx, int ds_agg, bool lines) {
+  if (ctx->opt.group_direct_blocks > 0) return (uint32_t)ctx->opt.group_direct_blocks;
+  static std::mutex mu;
+  static std::map<int, uint32_t> cus;
+  uint32_t cu = 0;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    uint32_t& c = cus[ctx->device];
+    if (!c) {
+      int v = 0;
+      c = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && v > 0
+              ? (uint32_t)v
+              : 1u;
+    }
+    cu = c;
+  }
+  auto bpc = [&](auto aggc) {
+    constexpr int A = decltype(aggc)::value;
+    return lines ? ug_direct_blocks_per_cu<A, true>() : ug_direct_blocks_per_cu<A, false>();
+  };
+  switch (ds_agg) {
+    case 0: return cu * bpc(std::integral_constant<int, 0>());
+    case 1: return cu * bpc(std::integral_constant<int, 1>());
+    case 2: return cu * bpc(std::integral_constant<int, 2>());
+    default: return cu * bpc(std::integral_constant<int, 3>());
+  }
+}
 
 // the aligned group (k_ug_ds_reg; sharded: one collective group and
 // k_fap_finish_end); RC_UG_FALLBACK when the group did not stand
@@ -2170,8 +2223,11 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
     // k_ds_reg, a wave a span, in the aligned group's mode, with the tail
     // in its last block (k_ug_ds_reg)
     // (direct: a wave takes a run of spans)
-    const uint32_t run = u.direct ? ug_direct_run(ctx->opt.group_direct_run, n_kept) : 1u;
-    const uint32_t rblocks = (uint32_t)(((uint64_t)n_kept + 4 * run - 1) / (4 * run));
+    const bool dlines = ug_direct_lines(ctx->opt.group_direct_load);
+    const int drun = ctx->opt.group_direct_run;
+    const uint32_t rblocks =
+        u.direct ? ug_direct_grid(drun, n_kept, drun <= 0 ? ug_direct_resident(ctx, d->ds_agg, dlines) : 0u)
+                 : (uint32_t)(((uint64_t)n_kept + 3) / 4);
     SpanDsArgs gr = {};
     gr.nseg = CK_NSEG;
     gr.seg_cap = 4u * ((rblocks + CK_NSEG - 1) / CK_NSEG);
@@ -2226,7 +2282,7 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
       const unsigned pad_direct = stat_lds_direct < UG_LDS_CAP ? UG_LDS_CAP - stat_lds_direct : 0u;
       EV_START(ctx, 8);
       if (u.direct) {
-        const bool lines = ug_direct_lines(ctx->opt.group_direct_load);
+        const bool lines = dlines;
         if (lines) ctx->gd_load_path = TSDBHIP_PATH_GROUP_DIRECT_LINES;
         auto direct = [&](auto k) {
           LAUNCH_STOP(EV_STOP_K(ctx, 9), k, dim3(rblocks), dim3(256), pad_direct, st, u.da, gr, u.row_ncells,
