@@ -26,6 +26,11 @@
  *       Tags.java:213-227, the ByteMap of group keys, the dropped spans of
  *       :339-344) and SpanGroup.getTags / getAggregatedTags of every group
  *       (computeTags, SpanGroup.java:149-191), from the spans' row keys.
+ *   tsdbhip_scan_rows — the Scanner of TsdbQuery.getScanner (TsdbQuery.java:
+ *       368-492: start / stop keys and createAndSetFilter's key regexp) over a
+ *       table of row keys, host or device resident.
+ *   tsdbhip_find_spans — the TreeMap under SpanCmp that TsdbQuery.findSpans
+ *       fills from the scanned rows (TsdbQuery.java:240-285, 594-621).
  *   tsdbhip_desc_gather — the repacking of the spans' rows into the plan's
  *       batch order for a descriptor already in HBM.
  *   tsdbhip_format_points  — the text GraphHandler.respondAsciiQuery,
@@ -415,6 +420,13 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *                   apart); "lines_nt", a wave instruction 1 KB contiguous with
  *                   non-temporal loads, transposed through LDS; "auto":
  *                   "lines_nt" (TSDBHIP_PATH_GROUP_DIRECT_LINES)
+ *   "scan_rows_load" "auto" | "lanes" | "lds"   how tsdbhip_scan_rows' match
+ *                   kernel reads the keys: "lanes", a lane its own key byte by
+ *                   byte; "lds", a wave the keys of its 64 rows in 16-byte
+ *                   pieces through LDS; "auto": "lds" 
+ *   "scan_rows_blocks" "auto" | a positive count   that kernel's grid at most
+ *                   (its waves stride over the table; a count lets a small
+ *                   table reach the second round: tests)
  *   "timing_detail" "on" | "off"   decode / grid event pairs in tsdbhip_timing
  *   "check_clean"   "on" | "off"   check the zero-on-entry invariants (stderr)
  *   "events"        "kernel" | "marker" | "none"   how tsdbhip_timing is measured:
@@ -644,6 +656,116 @@ typedef struct tsdbhip_spans_out {
 } tsdbhip_spans_out;
 
 int tsdbhip_find_spans(tsdbhip_ctx* ctx, const tsdbhip_scan_desc* scan, tsdbhip_spans_out* out);
+
+/* ---- getScanner: the rows of a query (an addition to ABI v8) ------------- */
+/*
+ * tsdbhip_scan_rows: the rows of a table that the Scanner of
+ * TsdbQuery.getScanner (TsdbQuery.java:368-394) delivers: those inside its
+ * start / stop keys (:378-388, getScanStartTime / getScanEndTime :396-425)
+ * whose key matches the regexp of createAndSetFilter (:433-492), which holds
+ * the fixed tags, the tag=* group-bys and the tag=v1|v2|... value lists of
+ * findGroupBys (:192-223). The selection is what tsdbhip_find_spans takes.
+ *
+ * Table: a tsdbhip_scan_desc, host or device resident (TSDBHIP_DESC_DEVICE).
+ * metric is the query's metric; rows may belong to any metric and come in any
+ * order; row_status and the four cell arrays (all or none) are optional and
+ * only gathered: row_status is passed through unread, the status and cell
+ * checks stay tsdbhip_find_spans' business.
+ *
+ * Key range, in 64 bits and then truncated as the reference's (int) does:
+ * scan_start = max(0, start_time - 2*3600 - sample_interval), scan_stop = the
+ * low 32 bits of end_time + 3600 + 1 + sample_interval, or 0xFFFFFFFF with
+ * TSDBHIP_SCAN_END_UNSET. A row is in range iff start_key <= key < stop_key,
+ * the keys being metric | time (big-endian), compared as HBase does: unsigned
+ * bytes, the shorter key first. For a well-shaped key: its metric bytes are
+ * the query's and scan_start <= base_time < scan_stop, unsigned. The wrap is
+ * reference behaviour: an end_time near 2^32 gives a stop below the start and
+ * selects nothing. A row of another metric is not selected; it is no error.
+ *
+ * Tag filter, applied only if n_tags + n_group_bys > 0: the items are the tags
+ * and group-bys merged in ascending name order (:455-488). The key's tag part
+ * must contain pairs, in that order, where pair i has item i's name and item
+ * i's value: the value of a fixed tag, any value for a group-by without value
+ * ids, one of the listed ids otherwise; any number of other pairs may stand
+ * before, between and after them ("(?:.{pair})*"). That is the regexp's
+ * language: a key's at most TSDBHIP_MAX_TAGS pairs are walked once, an item
+ * cursor advancing on the earliest match. The Java `$` may also match before
+ * a final line terminator (under ISO-8859-1 also 0x0D, 0x85 and \r\n); the
+ * rest of the pattern then has to cover a tag part that is one or two bytes
+ * short of a multiple of the pair width, which it cannot, so for a key whose
+ * tag part is a multiple of the pair width (the only keys accepted here) the
+ * result is the same. More than TSDBHIP_MAX_TAGS items in all: a valid query
+ * that matches no row.
+ *
+ * Errors, TSDBHIP_E_INVALID_ARG: a width outside 1..8; some but not all of
+ * the four cell arrays; a null required array; n_tags or n_group_bys above
+ * TSDBHIP_MAX_TAGS; tags or group_bys not strictly ascending by name; a name
+ * in both (the reference's AssertionError, :510-515); a null tags / group_bys
+ * / value array that the counts need. Then the key rules of
+ * tsdbhip_find_spans, over every row of the table, selected or not: key_off
+ * not ending at key_nbytes (before any row), decreasing or past key_nbytes; a
+ * key shorter than metric_width + 4, whose tag part is no multiple of
+ * name_width + value_width or holds more than TSDBHIP_MAX_TAGS pairs. Only
+ * the first offending row in table order counts, the message names it, and
+ * nothing is written. A host table is checked on the host before anything is
+ * staged, a device table by the match kernel, which proves every key byte
+ * inside key_bytes before reading it.
+ *
+ * Output: the selected rows in table order; the arrays are what a second
+ * tsdbhip_scan_desc takes (n_rows = n_selected, key_nbytes = key_used), so
+ * tsdbhip_find_spans runs on them unchanged. Cell offsets are passed through:
+ * cell bytes are never copied. row_capacity < n_selected or key_capacity <
+ * key_used: TSDBHIP_E_CAPACITY with both counts set for a retry and no array
+ * written. Nothing selected, also n_rows == 0: TSDBHIP_OK, the counts 0 and
+ * key_off[0] = 0 (when the array is given). For a device table every output
+ * is a device pointer, written in place; for a host table the outputs are
+ * host arrays.
+ *
+ * Value lists of any length (1024 ids and more) are fine; duplicates are
+ * allowed. tsdbhip_set_option: "scan_rows_load" "auto" | "lanes" | "lds" how
+ * the match kernel reads the keys (a lane its own key byte by byte, or a wave
+ * the contiguous keys of its 64 rows in 16-byte pieces through LDS; "auto":
+ * "lds"), "scan_rows_blocks" "auto" | a positive count: that kernel's
+ * grid at most (its waves stride over the table). Results never depend on
+ * either.
+ *
+ * tsdbhip_last_timing: total_ms, hot_ms (the match kernel), hot_kernel =
+ * TSDBHIP_HOT_SCAN_ROWS, alg_bytes = bytes read plus bytes written. A
+ * multi-device context runs the call on its first device.
+ */
+#define TSDBHIP_HAS_SCAN_ROWS 1
+#define TSDBHIP_HOT_SCAN_ROWS 12     /* k_sr_match: range and tag filter over every key of the table */
+#define TSDBHIP_SCAN_END_UNSET 0x1u  /* tsdbhip_scan_query.flags: end_time == UNSET, scan to 0xFFFFFFFF */
+
+typedef struct tsdbhip_scan_query {  /* every pointer is HOST memory */
+  uint32_t start_time, end_time;     /* getStartTime() / getEndTime(), seconds */
+  uint32_t sample_interval;          /* 0: none */
+  uint32_t flags;                    /* TSDBHIP_SCAN_END_UNSET */
+  uint32_t n_tags;                   /* 0..TSDBHIP_MAX_TAGS */
+  uint32_t n_group_bys;              /* 0..TSDBHIP_MAX_TAGS */
+  const uint8_t*  tags;              /* n_tags * (name_width + value_width): (name value), strictly ascending by name */
+  const uint8_t*  group_bys;         /* n_group_bys * name_width: names, strictly ascending */
+  const uint32_t* group_by_nvalues;  /* [n_group_bys] value ids of that group-by; 0: any value. NULL: all 0 */
+  const uint8_t*  group_by_values;   /* the ids, value_width bytes each, concatenated in group_bys order */
+} tsdbhip_scan_query;
+
+typedef struct tsdbhip_scan_sel {
+  uint32_t  row_capacity;      /* in */
+  uint32_t  n_selected;        /* out (also on E_CAPACITY) */
+  uint64_t  key_capacity;      /* in: bytes in key_bytes (key_nbytes of the table always suffices) */
+  uint64_t  key_used;          /* out (also on E_CAPACITY) */
+  uint32_t* row_index;         /* [row_capacity] index into the table of selected row i */
+  uint64_t* key_off;           /* [row_capacity+1] } what tsdbhip_scan_desc takes */
+  uint8_t*  key_bytes;         /* [key_capacity]   } */
+  uint8_t*  row_status;        /* [row_capacity] gathered if the table has it, else ignored */
+  uint64_t* row_qual_off;      /* [row_capacity] the four cell arrays likewise */
+  uint32_t* row_qual_len;
+  uint64_t* row_val_off;
+  uint32_t* row_val_len;
+} tsdbhip_scan_sel;
+
+int tsdbhip_scan_rows(tsdbhip_ctx* ctx, const tsdbhip_scan_desc* table, const tsdbhip_scan_query* query,
+                      tsdbhip_scan_sel* out);
 
 /* ---- output formatting (host cores, no GPU) ----------------------------- */
 /*

@@ -255,6 +255,45 @@ class SpansOut(C.Structure):
     ]
 
 
+HOT_SCAN_ROWS = 12
+HOT_NAMES[HOT_SCAN_ROWS] = "k_sr_match"
+SCAN_END_UNSET = 0x1  # tsdbhip_scan_query.flags
+
+
+class ScanQuery(C.Structure):
+    """tsdbhip_scan_query: the scanner's key range and tag filter (host memory)"""
+    _fields_ = [
+        ("start_time", C.c_uint32),
+        ("end_time", C.c_uint32),
+        ("sample_interval", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("n_tags", C.c_uint32),
+        ("n_group_bys", C.c_uint32),
+        ("tags", P8),
+        ("group_bys", P8),
+        ("group_by_nvalues", P32),
+        ("group_by_values", P8),
+    ]
+
+
+class ScanSel(C.Structure):
+    """tsdbhip_scan_sel: the selected rows (arrays owned by the caller, host or device as the table's)"""
+    _fields_ = [
+        ("row_capacity", C.c_uint32),
+        ("n_selected", C.c_uint32),
+        ("key_capacity", C.c_uint64),
+        ("key_used", C.c_uint64),
+        ("row_index", P32),
+        ("key_off", P64),
+        ("key_bytes", P8),
+        ("row_status", P8),
+        ("row_qual_off", P64),
+        ("row_qual_len", P32),
+        ("row_val_off", P64),
+        ("row_val_len", P32),
+    ]
+
+
 def ptr(arr, ctype):
     """numpy array -> ctypes pointer (array must stay alive)."""
     return arr.ctypes.data_as(C.POINTER(ctype))

@@ -776,6 +776,251 @@ def query_run(ctx, rows, metric, group_bys, start_time, end_time, rate, aggregat
                                   ctx, metric_width, name_width, value_width, device_plan=device, tsdb=tsdb)
 
 
+# --------------------------------------------------------------- getScanner ----
+def scan_times(start_time, end_time, interval=0):
+    """(scan_start, scan_stop) of TsdbQuery.getScanner (TsdbQuery.java:378-382,
+    396-425): 64-bit arithmetic, then (int). end_time None: UNSET, the stop key
+    is metric | 0xFFFFFFFF."""
+    ts = int(start_time) - 2 * 3600 - int(interval)
+    stop = 0xFFFFFFFF if end_time is None else (int(end_time) + 3600 + 1 + int(interval)) & 0xFFFFFFFF
+    return (ts if ts > 0 else 0) & 0xFFFFFFFF, stop
+
+
+def _scan_items(tags, group_bys, group_by_values, name_width, value_width):
+    """the checks of tsdbhip_scan_rows on a query, in its order, and the items
+    of createAndSetFilter's merge (:455-488): [(name, None: any | set of ids)]"""
+    tags = [(bytes(n), bytes(v)) for n, v in (tags.items() if isinstance(tags, dict) else (tags or []))]
+    gbs = [bytes(g) for g in (group_bys or [])]
+    if len(tags) > _abi.MAX_TAGS:
+        raise ValueError("more than TSDBHIP_MAX_TAGS tags")
+    if len(gbs) > _abi.MAX_TAGS:
+        raise ValueError("more than TSDBHIP_MAX_TAGS group_bys")
+    for n, v in tags:
+        if len(n) != name_width or len(v) != value_width:
+            raise ValueError("a tag of the wrong width")
+    if any(len(g) != name_width for g in gbs):
+        raise ValueError("a group_by of the wrong width")
+    if any(a[0] >= b[0] for a, b in zip(tags, tags[1:])):
+        raise ValueError("tags not strictly ascending by name")
+    if any(a >= b for a, b in zip(gbs, gbs[1:])):
+        raise ValueError("group_bys not strictly ascending")
+    if {n for n, _ in tags} & set(gbs):
+        raise ValueError("a name is both in tags and in group_bys")  # the AssertionError of :510-515
+    gbv = {bytes(k): [bytes(x) for x in v] for k, v in (group_by_values or {}).items() if v}
+    if any(len(x) != value_width for v in gbv.values() for x in v):
+        raise ValueError("a value id of the wrong width")
+    items = [(n, {v}) for n, v in tags] + [(g, set(gbv[g]) if g in gbv else None) for g in gbs]
+    return tags, gbs, gbv, sorted(items, key=lambda it: it[0])
+
+
+def _key_of(row):
+    return bytes(row[0]) if isinstance(row, (tuple, list)) else bytes(row)
+
+
+def scan_rows(rows, metric, tags=None, group_bys=None, group_by_values=None, start_time=0, end_time=None, interval=0,
+              metric_width=3, name_width=3, value_width=3):
+    """The rows the Scanner of TsdbQuery.getScanner delivers (TsdbQuery.java:
+    368-394), restated on the host: `rows` is the table, row keys or find_spans'
+    (row_key, KeyValue) pairs, of any metric in any order; tags the fixed
+    (name id, value id) pairs, ascending by name; group_bys the name ids,
+    ascending; group_by_values {name id: [value ids]} (absent or empty: any
+    value, the tag=* of findGroupBys :192-223); end_time None: UNSET. Returns
+    the indices of the selected rows, in table order: inside the start / stop
+    keys and matching createAndSetFilter's regexp (:433-492), decided by walking
+    the key's pairs once with an item cursor. ValueError: what
+    tsdbhip_scan_rows answers TSDBHIP_E_INVALID_ARG to."""
+    if not all(1 <= w <= 8 for w in (metric_width, name_width, value_width)):
+        raise ValueError("a width outside 1..8")
+    _, _, _, items = _scan_items(tags, group_bys, group_by_values, name_width, value_width)
+    t0, t1 = scan_times(start_time, end_time, interval)
+    metric = bytes(metric)[:metric_width]
+    hdr, pair = metric_width + 4, name_width + value_width
+    keys = [_key_of(r) for r in rows]
+    for i, k in enumerate(keys):
+        if len(k) < hdr or (len(k) - hdr) % pair or (len(k) - hdr) // pair > _abi.MAX_TAGS:
+            raise ValueError(f"bad row key length at row {i}")
+    sel = []
+    for i, k in enumerate(keys):
+        if k[:metric_width] != metric or not t0 <= int.from_bytes(k[metric_width:hdr], "big") < t1:
+            continue
+        if items:
+            if len(items) > _abi.MAX_TAGS:
+                continue
+            cur = 0
+            for pos in range(hdr, len(k), pair):
+                if cur == len(items):
+                    break
+                name, vals = items[cur]
+                if k[pos:pos + name_width] == name and (vals is None or k[pos + name_width:pos + pair] in vals):
+                    cur += 1
+            if cur != len(items):
+                continue
+        sel.append(i)
+    return sel
+
+
+class ScanSelection:
+    """tsdbhip_scan_sel as numpy arrays (trimmed to what the call set); on an
+    error only the counts, and .raw = the untouched output arrays."""
+
+    FIELDS = ("row_index", "key_off", "key_bytes", "row_status", "row_qual_off", "row_qual_len", "row_val_off",
+              "row_val_len")
+
+    def __init__(self, out, arrays, ok):
+        self.n_selected, self.key_used = int(out.n_selected), int(out.key_used)
+        self.raw = arrays
+        if not ok:
+            return
+        for f in self.FIELDS:
+            a = arrays.get(f)
+            if a is None or isinstance(a, int):
+                setattr(self, f, None)
+            elif f == "key_off":
+                setattr(self, f, a[:self.n_selected + 1])
+            elif f == "key_bytes":
+                setattr(self, f, a[:self.key_used])
+            else:
+                setattr(self, f, a[:self.n_selected])
+
+    def keys(self):
+        kb = self.key_bytes.tobytes()
+        return [kb[int(self.key_off[s]):int(self.key_off[s + 1])] for s in range(self.n_selected)]
+
+
+def make_scan_query(tags, group_bys, group_by_values, start_time, end_time, interval, name_width=3, value_width=3):
+    """(tsdbhip_scan_query, the arrays it points to): no check is made here,
+    the library makes them"""
+    tags = [(bytes(n), bytes(v)) for n, v in (tags.items() if isinstance(tags, dict) else (tags or []))]
+    gbs = [bytes(g) for g in (group_bys or [])]
+    gbv = {bytes(k): [bytes(x) for x in v] for k, v in (group_by_values or {}).items()}
+    q = _abi.ScanQuery()
+    q.start_time = int(start_time)
+    q.end_time = 0 if end_time is None else int(end_time)
+    q.sample_interval = int(interval)
+    q.flags = _abi.SCAN_END_UNSET if end_time is None else 0
+    q.n_tags, q.n_group_bys = len(tags), len(gbs)
+    t = np.frombuffer(b"".join(n + v for n, v in tags) + b"\0", np.uint8).copy()
+    g = np.frombuffer(b"".join(gbs) + b"\0", np.uint8).copy()
+    nv = np.array([len(gbv.get(x, ())) for x in gbs] + [0], np.uint32)
+    v = np.frombuffer(b"".join(b"".join(gbv.get(x, ())) for x in gbs) + b"\0", np.uint8).copy()
+    q.tags, q.group_bys = _abi.ptr(t, C.c_uint8), _abi.ptr(g, C.c_uint8)
+    q.group_by_nvalues, q.group_by_values = _abi.ptr(nv, C.c_uint32), _abi.ptr(v, C.c_uint8)
+    return q, (t, g, nv, v)
+
+
+def run_scan_rows(ctx, key_off, key_bytes, metric, query, status=None, cells=None, metric_width=3, name_width=3,
+                  value_width=3, row_capacity=None, key_capacity=None, device=False, n_rows=None, key_nbytes=None,
+                  outputs=None):
+    """Low-level: one tsdbhip_scan_rows over a table. key_off / key_bytes /
+    status and cells = (qual_off, qual_len, val_off, val_len) are numpy arrays,
+    or with device=True device addresses (ints; n_rows and key_nbytes then
+    given, and outputs = {field: device address} of the caller's output arrays,
+    row_capacity / key_capacity their sizes). query: a tsdbhip_scan_query
+    (make_scan_query). outputs may also pre-fill host arrays (the tests'
+    sentinels). Returns (code, ScanSelection)."""
+    d = _abi.ScanDesc()
+    keep = []
+
+    def inp(a, dtype, ptype):
+        if a is None:
+            return None
+        if device:
+            return C.cast(C.c_void_p(int(a)), ptype)
+        a = np.ascontiguousarray(a, dtype)
+        keep.append(a)
+        return a.ctypes.data_as(ptype)
+
+    if device:
+        n, nbytes = int(n_rows), int(key_nbytes)
+        d.flags = _abi.DESC_DEVICE
+    else:
+        n = (len(key_off) - 1 if key_off is not None else 0) if n_rows is None else int(n_rows)
+        nbytes = (len(key_bytes) if key_bytes is not None else 0) if key_nbytes is None else int(key_nbytes)
+    for f, a, dt, pt in (("key_off", key_off, np.uint64, _abi.P64), ("key_bytes", key_bytes, np.uint8, _abi.P8),
+                         ("row_status", status, np.uint8, _abi.P8)):
+        p = inp(a, dt, pt)
+        if p is not None:
+            setattr(d, f, p)
+    if cells is not None:
+        for f, a, dt, pt in zip(("row_qual_off", "row_qual_len", "row_val_off", "row_val_len"), cells,
+                                (np.uint64, np.uint32, np.uint64, np.uint32),
+                                (_abi.P64, _abi.P32, _abi.P64, _abi.P32)):
+            p = inp(a, dt, pt)
+            if p is not None:
+                setattr(d, f, p)
+    m = np.frombuffer(bytes(metric) + b"\0" * 8, np.uint8).copy()
+    d.metric = _abi.ptr(m, C.c_uint8)
+    d.n_rows, d.key_nbytes = n, nbytes
+    d.metric_width, d.name_width, d.value_width = int(metric_width), int(name_width), int(value_width)
+    rcap = max(1, n) if row_capacity is None else int(row_capacity)
+    kcap = max(1, nbytes) if key_capacity is None else int(key_capacity)
+    out = _abi.ScanSel()
+    out.row_capacity, out.key_capacity = rcap, kcap
+    types = {"row_index": (np.uint32, _abi.P32, max(1, rcap)), "key_off": (np.uint64, _abi.P64, rcap + 1),
+             "key_bytes": (np.uint8, _abi.P8, max(1, kcap)), "row_status": (np.uint8, _abi.P8, max(1, rcap)),
+             "row_qual_off": (np.uint64, _abi.P64, max(1, rcap)), "row_qual_len": (np.uint32, _abi.P32, max(1, rcap)),
+             "row_val_off": (np.uint64, _abi.P64, max(1, rcap)), "row_val_len": (np.uint32, _abi.P32, max(1, rcap))}
+    arrays = {}
+    for f, (dt, pt, size) in types.items():
+        if device:
+            a = (outputs or {}).get(f)
+            if a is not None:
+                arrays[f] = int(a)
+                setattr(out, f, C.cast(C.c_void_p(int(a)), pt))
+            continue
+        if outputs is not None and f in outputs:
+            a = outputs[f]
+            if a is None:  # (a null output array, for the argument checks)
+                arrays[f] = None
+                continue
+        elif (status is None and f == "row_status") or (cells is None and f.startswith("row_") and f != "row_index"
+                                                        and f != "row_status"):
+            continue
+        else:
+            a = np.zeros(size, dt)
+        assert a.dtype == dt and a.flags.c_contiguous
+        arrays[f] = a
+        setattr(out, f, a.ctypes.data_as(pt))
+    rc = ctx._lib.tsdbhip_scan_rows(ctx.handle, C.byref(d), C.byref(query), C.byref(out))
+    return rc, ScanSelection(out, arrays, rc == 0)
+
+
+def scan_rows_device(ctx, rows, metric, tags=None, group_bys=None, group_by_values=None, start_time=0, end_time=None,
+                     interval=0, metric_width=3, name_width=3, value_width=3):
+    """scan_rows on the GPU (tsdbhip_scan_rows): the same indices."""
+    keys = [_key_of(r) for r in rows]
+    key_off = np.zeros(len(keys) + 1, np.uint64)
+    if keys:
+        key_off[1:] = np.cumsum([len(k) for k in keys])
+    key_bytes = np.frombuffer(b"".join(keys), np.uint8).copy()
+    q, keep = make_scan_query(tags, group_bys, group_by_values, start_time, end_time, interval, name_width, value_width)
+    rc, sel = run_scan_rows(ctx, key_off, key_bytes, metric, q, None, None, metric_width, name_width, value_width)
+    if rc:
+        raise _exception_for(rc, ctx.last_error())
+    return sel.row_index.tolist()
+
+
+def tsdb_query_run(ctx, table_rows, metric, tags, group_bys, group_by_values, start_time, end_time, rate, aggregator,
+                   interval=0, downsampler=None, metric_width=3, name_width=3, value_width=3, device=False,
+                   tsdb=None):
+    """TsdbQuery.run from the table on: the scanner (scan_rows; device:
+    tsdbhip_scan_rows) over table_rows, find_spans' (row_key, KeyValue | None)
+    pairs of any metric, then query_run over the rows it delivers. The
+    scanner looks further than the query's times (:396-425) with the
+    downsampling interval as sample_interval, as the reference sets it."""
+    scan = scan_rows_device if device else scan_rows
+    args = (table_rows, metric, tags, group_bys, group_by_values, start_time, end_time, interval, metric_width,
+            name_width, value_width)
+    sel = scan(ctx, *args) if device else scan(*args)
+    rows = [table_rows[i] for i in sel]
+    return query_run(ctx, rows, metric, group_bys, start_time, U32_END if end_time is None else end_time, rate,
+                     aggregator, interval, downsampler, metric_width, name_width, value_width, device=device,
+                     tsdb=tsdb)
+
+
+U32_END = 0xFFFFFFFF
+
+
 # ------------------------------------------------------------ output text ----
 FMT_ASCII, FMT_GNUPLOT, FMT_CLI = 0, 1, 2
 

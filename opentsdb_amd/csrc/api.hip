@@ -43,6 +43,7 @@
 #include "k_group.hip"
 #include "k_groupby.hip"
 #include "k_findspans.hip"
+#include "k_scanrows.hip"
 
 using namespace tsdb;
 
@@ -76,6 +77,9 @@ struct Options {
                                // device's), or a count (small test groups reach long runs with it)
   int group_direct_load = -1;  // "group_direct_load": that launch's chunk loader (reg_run's LINES): "auto" (-1:
                                // ug_direct_lines()), "rows" (0), "lines_nt" (1)
+  int scan_rows_load = -1;     // "scan_rows_load": k_sr_match's key loader: "auto" (-1: sr_auto_lds()), "lanes" (0),
+                               // "lds" (1)
+  int scan_rows_blocks = 0;    // "scan_rows_blocks": that kernel's grid at most: "auto" (0: SR_BLOCKS), or a count
   bool timing_detail = false;  // "timing_detail": decode / grid event pairs (tsdbhip_timing)
   bool check_clean = false;    // "check_clean": verify the zero-on-entry invariants (stderr)
   int events = 0;              // "events": timing events on kernel launches (0), marker packets (1), none (2)
@@ -597,6 +601,17 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
     ok = false;
     for (int i = 0; i < 3; i++)
       if (v == names[i]) { o.group_direct_load = i - 1; ok = true; }
+  }
+  else if (n == "scan_rows_load") {
+    static const char* names[] = {"auto", "lanes", "lds"};
+    ok = false;
+    for (int i = 0; i < 3; i++)
+      if (v == names[i]) { o.scan_rows_load = i - 1; ok = true; }
+  }
+  else if (n == "scan_rows_blocks") {
+    const long b = v == "auto" ? 0 : std::strtol(v.c_str(), nullptr, 10);
+    ok = v == "auto" || (b > 0 && b <= (1 << 20) && v.find_first_not_of("0123456789") == std::string::npos);
+    o.scan_rows_blocks = (int)b;
   }
   else if (n == "timing_detail") ok = on_off(o.timing_detail);
   else if (n == "check_clean") ok = on_off(o.check_clean);
@@ -4633,3 +4648,4 @@ extern "C" int tsdbhip_bw_probe(tsdbhip_ctx* c, const tsdbhip_sg_desc* d, int32_
 
 #include "groupby.hip"
 #include "findspans.hip"
+#include "scanrows.hip"

@@ -50,14 +50,23 @@ struct FsRow {
   bool added;        // status != NONE
 };
 
+// A key at key[o0, o1): 0, or FS_E_OFF / FS_E_SHAPE (the part of the row
+// check that tsdbhip_scan_rows shares, scanrows_host.h). Reads no key byte.
+FS_HD uint32_t fs_check_key(const FsRows& a, uint64_t o0, uint64_t o1) {
+  const uint32_t pair = a.nw + a.vw, hdr = a.mw + 4;
+  if (!(o0 <= o1 && o1 <= a.key_nbytes)) return FS_E_OFF;
+  const uint64_t len = o1 - o0;
+  if (len < hdr || (len - hdr) % pair != 0 || (len - hdr) / pair > TSDBHIP_MAX_TAGS) return FS_E_SHAPE;
+  return 0;
+}
+
 // Row r (r < a.n): 0 and *row filled in, or the class of what is wrong with
 // it. No key byte is read before it is proven inside [0, key_nbytes).
 FS_HD uint32_t fs_check_row(const FsRows& a, uint32_t r, FsRow* row) {
   const uint32_t pair = a.nw + a.vw, hdr = a.mw + 4;
   const uint64_t o0 = a.key_off[r], o1 = a.key_off[r + 1];
-  if (!(o0 <= o1 && o1 <= a.key_nbytes)) return FS_E_OFF;
+  if (const uint32_t cls = fs_check_key(a, o0, o1)) return cls;
   const uint64_t len = o1 - o0;
-  if (len < hdr || (len - hdr) % pair != 0 || (len - hdr) / pair > TSDBHIP_MAX_TAGS) return FS_E_SHAPE;
   const uint32_t st = a.status ? a.status[r] : (uint32_t)TSDBHIP_ROW_SINGLE;
   if (st > TSDBHIP_ROW_OOB) return FS_E_STATUS;
   const bool added = st != TSDBHIP_ROW_NONE && st != TSDBHIP_ROW_ERROR && st != TSDBHIP_ROW_OOB;
