@@ -33,6 +33,9 @@
  *       fills from the scanned rows (TsdbQuery.java:240-285, 594-621).
  *   tsdbhip_desc_gather — the repacking of the spans' rows into the plan's
  *       batch order for a descriptor already in HBM.
+ *   tsdbhip_desc_pack — the bridge's copy of each compacted KeyValue to aligned
+ *       offsets (TsdbQuery.java:264-266 as packing.pack_spans does it) for a
+ *       descriptor already in HBM.
  *   tsdbhip_format_points  — the text GraphHandler.respondAsciiQuery,
  *       Plot.dumpToFiles and CliQuery print for each DataPoint.
  *   tsdbhip_compact_rows   — CompactionQueue.compact(row, compacted[])
@@ -427,6 +430,10 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *   "scan_rows_blocks" "auto" | a positive count   that kernel's grid at most
  *                   (its waves stride over the table; a count lets a small
  *                   table reach the second round: tests)
+ *   "desc_pack_load" "auto" | "unaligned" | "shift"   how tsdbhip_desc_pack's copy
+ *                   kernel loads a row's bytes: "unaligned", one load of the
+ *                   store's width at the row's own residue; "shift", dword-aligned
+ *                   loads and v_alignbyte_b32; "auto": "unaligned" 
  *   "timing_detail" "on" | "off"   decode / grid event pairs in tsdbhip_timing
  *   "check_clean"   "on" | "off"   check the zero-on-entry invariants (stderr)
  *   "events"        "kernel" | "marker" | "none"   how tsdbhip_timing is measured:
@@ -766,6 +773,63 @@ typedef struct tsdbhip_scan_sel {
 
 int tsdbhip_scan_rows(tsdbhip_ctx* ctx, const tsdbhip_scan_desc* table, const tsdbhip_scan_query* query,
                       tsdbhip_scan_sel* out);
+
+/* ---- repacking device rows to the streaming layout (an addition to ABI v8) - */
+/*
+ * tsdbhip_desc_pack: the spans order[0..n) of the device-resident descriptor
+ * `in`, like tsdbhip_desc_gather, with their rows' bytes COPIED into new
+ * buffers in packing.pack_spans' layout: the layout the streaming kernels take
+ * (qualifiers at 0 mod 8, values at 0 mod 16; see tsdbhip_sg_desc), which
+ * tsdbhip_compact_rows' placement and a gathered descriptor miss.
+ *
+ * Input: `in` must be device resident (TSDBHIP_DESC_DEVICE) and not
+ * TSDBHIP_SHARDED, and in != out; else TSDBHIP_E_INVALID_ARG. order is a host
+ * array of n span indices, order[i] >= in->n_spans: TSDBHIP_E_INVALID_ARG; a
+ * span may appear more than once. order == NULL: every span of `in` in its own
+ * order, and n must equal in->n_spans.
+ *
+ * Output: `out` receives the query fields and flags of `in`, n_spans = n,
+ * n_rows = the gathered row count, span0 = 0. span_row_start, row_base,
+ * row_ncells and row_val_len are what tsdbhip_desc_gather returns for the same
+ * arguments. Gathered row i lies at
+ *   row_qual_off[i] = sum over j < i of align8(2 * row_ncells[j])
+ *   row_val_off[i]  = sum over j < i of align16(row_val_len[j])     (64 bits)
+ * and qual_nbytes = align16(max(sum of align8, 1)), val_nbytes likewise from
+ * the sum of align16. Every row's bytes are copied unchanged, every byte of
+ * [0, nbytes) outside a row is 0, and the allocations are readable and zero
+ * for 64 bytes past nbytes: the eight arrays are byte for byte what
+ * packing.pack_spans returns for the same rows. All eight are new device
+ * allocations owned by ctx; `out` needs nothing from `in` afterwards.
+ * tsdbhip_desc_pack_free releases them and zeroes the eight pointers and the
+ * two nbytes; a second call is harmless. (tsdbhip_desc_gather_free does not
+ * release a packed descriptor.) Packing into an `out` that already holds a
+ * packed descriptor releases the earlier one once the new one stands.
+ *
+ * Source rows may lie at any offset, odd qualifier offsets included: this is a
+ * byte copy. A gathered row with row_qual_off + 2 * row_ncells > in->qual_nbytes
+ * or row_val_off + row_val_len > in->val_nbytes: TSDBHIP_E_INVALID_ARG; only the
+ * first offending gathered row counts, the message names it, *out is left
+ * untouched, and the check runs before any byte is read. The call reads
+ * nothing before in->qual_bytes / in->val_bytes and nothing at or beyond
+ * nbytes + 64 (the slack TSDBHIP_DESC_DEVICE requires), and never writes to
+ * `in`.
+ *
+ * tsdbhip_set_option "desc_pack_load" "auto" | "unaligned" | "shift": how the
+ * copy kernel loads a row's bytes: "unaligned", one 16-byte (qualifiers:
+ * 8-byte) load at the row's own residue; "shift", dword-aligned loads and
+ * v_alignbyte_b32 by the residue; "auto": "unaligned" (DESIGN.md). Results
+ * never depend on it.
+ *
+ * tsdbhip_last_timing: total_ms, hot_ms (the copy kernel), hot_kernel =
+ * TSDBHIP_HOT_DESC_PACK, alg_bytes = row bytes read + buffer bytes written +
+ * metadata read and written. A multi-device context runs the call on its
+ * first device.
+ */
+#define TSDBHIP_HAS_DESC_PACK 1
+#define TSDBHIP_HOT_DESC_PACK 13   /* k_pack_copy */
+int tsdbhip_desc_pack(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* in, const uint32_t* order, uint32_t n,
+                      tsdbhip_sg_desc* out);
+int tsdbhip_desc_pack_free(tsdbhip_ctx* ctx, tsdbhip_sg_desc* out);
 
 /* ---- output formatting (host cores, no GPU) ----------------------------- */
 /*

@@ -294,6 +294,10 @@ class ScanSel(C.Structure):
     ]
 
 
+HOT_DESC_PACK = 13
+HOT_NAMES[HOT_DESC_PACK] = "k_pack_copy"
+
+
 def ptr(arr, ctype):
     """numpy array -> ctypes pointer (array must stay alive)."""
     return arr.ctypes.data_as(C.POINTER(ctype))

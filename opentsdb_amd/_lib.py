@@ -26,7 +26,7 @@ EXPORTS = [
     "tsdbhip_format_points", "tsdbhip_open_devices", "tsdbhip_open_mask", "tsdbhip_ranks",
     "tsdbhip_timing_totals", "tsdbhip_set_option",
     "tsdbhip_groupby_plan", "tsdbhip_desc_gather", "tsdbhip_desc_gather_free",
-    "tsdbhip_find_spans", "tsdbhip_scan_rows",
+    "tsdbhip_find_spans", "tsdbhip_scan_rows", "tsdbhip_desc_pack", "tsdbhip_desc_pack_free",
 ]
 
 
@@ -103,6 +103,10 @@ def lib():
     L.tsdbhip_find_spans.restype = C.c_int
     L.tsdbhip_scan_rows.argtypes = [C.c_void_p, P(_abi.ScanDesc), P(_abi.ScanQuery), P(_abi.ScanSel)]
     L.tsdbhip_scan_rows.restype = C.c_int
+    L.tsdbhip_desc_pack.argtypes = [C.c_void_p, P(_abi.SgDesc), P(C.c_uint32), C.c_uint32, P(_abi.SgDesc)]
+    L.tsdbhip_desc_pack.restype = C.c_int
+    L.tsdbhip_desc_pack_free.argtypes = [C.c_void_p, P(_abi.SgDesc)]
+    L.tsdbhip_desc_pack_free.restype = C.c_int
     if L.tsdbhip_abi_version() != _abi.ABI_VERSION:
         raise TsdbHipError(_abi.E_INVALID_ARG, "ABI version mismatch")
     _LIB = L

@@ -1021,6 +1021,56 @@ def tsdb_query_run(ctx, table_rows, metric, tags, group_bys, group_by_values, st
 U32_END = 0xFFFFFFFF
 
 
+# ------------------------------------------- repacking a device descriptor ----
+def pack_offsets(row_ncells, row_val_len):
+    """The placement rule of packing.pack_spans and tsdbhip_desc_pack for rows
+    of these lengths, in row order: (row_qual_off, row_val_off, qual_nbytes,
+    val_nbytes). Row i's qualifiers lie at the sum of align8(2 ncells) of the
+    rows before it, its values at the sum of align16(val_len); a buffer is
+    align16(max(that sum over every row, 1)) bytes long."""
+    qsz = (2 * np.asarray(row_ncells, np.uint64) + np.uint64(7)) & ~np.uint64(7)
+    vsz = (np.asarray(row_val_len, np.uint64) + np.uint64(15)) & ~np.uint64(15)
+    qend = np.cumsum(qsz, dtype=np.uint64)
+    vend = np.cumsum(vsz, dtype=np.uint64)
+    q_used = int(qend[-1]) if len(qend) else 0
+    v_used = int(vend[-1]) if len(vend) else 0
+    return qend - qsz, vend - vsz, (max(q_used, 1) + 15) // 16 * 16, (max(v_used, 1) + 15) // 16 * 16
+
+
+def run_desc_pack(ctx, desc, order=None):
+    """Low-level: one tsdbhip_desc_pack of the device-resident SgDesc `desc`
+    (order: span indices, None: every span in its own order). Returns (code,
+    SgDesc): the packed descriptor's arrays belong to the context until
+    tsdbhip_desc_pack_free (PackedDesc frees on exit)."""
+    out = _abi.SgDesc()
+    if order is None:
+        rc = ctx._lib.tsdbhip_desc_pack(ctx.handle, C.byref(desc), None, desc.n_spans, C.byref(out))
+    else:
+        o = np.ascontiguousarray(order, np.uint32)
+        rc = ctx._lib.tsdbhip_desc_pack(ctx.handle, C.byref(desc), _abi.ptr(o, C.c_uint32), len(o), C.byref(out))
+    return rc, out
+
+
+class PackedDesc:
+    """`with PackedDesc(ctx, desc, order) as d:` d is the packed SgDesc; a
+    failed pack raises, the arrays are freed on exit."""
+
+    def __init__(self, ctx, desc, order=None):
+        self.ctx, self.src, self.order, self.desc = ctx, desc, order, None
+
+    def __enter__(self):
+        rc, d = run_desc_pack(self.ctx, self.src, self.order)
+        if rc:
+            raise _exception_for(rc, self.ctx.last_error())
+        self.desc = d
+        return d
+
+    def __exit__(self, *exc):
+        if self.desc is not None:
+            self.ctx._lib.tsdbhip_desc_pack_free(self.ctx.handle, C.byref(self.desc))
+        return False
+
+
 # ------------------------------------------------------------ output text ----
 FMT_ASCII, FMT_GNUPLOT, FMT_CLI = 0, 1, 2
 

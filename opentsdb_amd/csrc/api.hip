@@ -44,6 +44,7 @@
 #include "k_groupby.hip"
 #include "k_findspans.hip"
 #include "k_scanrows.hip"
+#include "k_descpack.hip"
 
 using namespace tsdb;
 
@@ -80,6 +81,8 @@ struct Options {
   int scan_rows_load = -1;     // "scan_rows_load": k_sr_match's key loader: "auto" (-1: sr_auto_lds()), "lanes" (0),
                                // "lds" (1)
   int scan_rows_blocks = 0;    // "scan_rows_blocks": that kernel's grid at most: "auto" (0: SR_BLOCKS), or a count
+  int desc_pack_load = -1;     // "desc_pack_load": k_pack_copy's source loader: "auto" (-1: pack_auto_shift()),
+                               // "unaligned" (0), "shift" (1)
   bool timing_detail = false;  // "timing_detail": decode / grid event pairs (tsdbhip_timing)
   bool check_clean = false;    // "check_clean": verify the zero-on-entry invariants (stderr)
   int events = 0;              // "events": timing events on kernel launches (0), marker packets (1), none (2)
@@ -612,6 +615,12 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
     const long b = v == "auto" ? 0 : std::strtol(v.c_str(), nullptr, 10);
     ok = v == "auto" || (b > 0 && b <= (1 << 20) && v.find_first_not_of("0123456789") == std::string::npos);
     o.scan_rows_blocks = (int)b;
+  }
+  else if (n == "desc_pack_load") {
+    static const char* names[] = {"auto", "unaligned", "shift"};
+    ok = false;
+    for (int i = 0; i < 3; i++)
+      if (v == names[i]) { o.desc_pack_load = i - 1; ok = true; }
   }
   else if (n == "timing_detail") ok = on_off(o.timing_detail);
   else if (n == "check_clean") ok = on_off(o.check_clean);
@@ -4649,3 +4658,4 @@ extern "C" int tsdbhip_bw_probe(tsdbhip_ctx* c, const tsdbhip_sg_desc* d, int32_
 #include "groupby.hip"
 #include "findspans.hip"
 #include "scanrows.hip"
+#include "descpack.hip"
