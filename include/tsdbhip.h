@@ -36,7 +36,10 @@
  *   tsdbhip_desc_pack — the bridge's copy of each compacted KeyValue to aligned
  *       offsets (TsdbQuery.java:264-266 as packing.pack_spans does it) for a
  *       descriptor already in HBM.
- *   tsdbhip_format_points  — the text GraphHandler.respondAsciiQuery,
+ *   tsdbhip_desc_certify — no counterpart: the proof, made once for a resident
+ *       table, that every row's qualifiers are regular (the streaming kernels
+ *       then read the values alone).
+ *   tsdbhip_format_points — the text GraphHandler.respondAsciiQuery,
  *       Plot.dumpToFiles and CliQuery print for each DataPoint.
  *   tsdbhip_compact_rows   — CompactionQueue.compact(row, compacted[])
  *       (CompactionQueue.java:243-435, 450-743) for a batch of rows.
@@ -118,6 +121,9 @@ extern "C" {
 #define TSDBHIP_SHARDED       0x4u /* desc holds this rank's shard of the
                                       group; exchange with the other ranks of
                                       the communicator set by tsdbhip_comm_init */
+#define TSDBHIP_DESC_QUALS_PROVEN 0x8u /* (with TSDBHIP_DESC_DEVICE) the rows'
+                                      qualifiers were proven regular and have
+                                      not changed since: tsdbhip_desc_certify */
 
 typedef struct tsdbhip_ctx tsdbhip_ctx;
 
@@ -267,6 +273,10 @@ typedef struct tsdbhip_timing {
 #define TSDBHIP_PATH_GROUP_DIRECT_LINES 256u  /* that launch (taken or fallen
                                           back) read the values in whole lines
                                           ("group_direct_load" lines_nt)      */
+#define TSDBHIP_PATH_QUALS_PROVEN 512u  /* that launch (taken or fallen back)
+                                          ran without the qualifier stream: the
+                                          descriptor carried
+                                          TSDBHIP_DESC_QUALS_PROVEN             */
 
 /* ---- row compaction (CompactionQueue.compact) -------------------------- */
 /*
@@ -423,6 +433,13 @@ int         tsdbhip_open_devices(const int32_t* devices, uint32_t n, tsdbhip_ctx
  *                   apart); "lines_nt", a wave instruction 1 KB contiguous with
  *                   non-temporal loads, transposed through LDS; "auto":
  *                   "lines_nt" (TSDBHIP_PATH_GROUP_DIRECT_LINES)
+ *   "quals_proven"  "auto" | "off" | "rank0"   "auto": that launch does not read
+ *                   the qualifiers of a device descriptor that carries
+ *                   TSDBHIP_DESC_QUALS_PROVEN (TSDBHIP_PATH_QUALS_PROVEN); "off":
+ *                   it reads and proves them on every call whatever the flag;
+ *                   "rank0": "auto" on rank 0 of a sharded call and "off" on
+ *                   every other rank (tests: the ranks of a multi-device
+ *                   context share one descriptor). Results never depend on it
  *   "scan_rows_load" "auto" | "lanes" | "lds"   how tsdbhip_scan_rows' match
  *                   kernel reads the keys: "lanes", a lane its own key byte by
  *                   byte; "lds", a wave the keys of its 64 rows in 16-byte
@@ -830,6 +847,57 @@ int tsdbhip_scan_rows(tsdbhip_ctx* ctx, const tsdbhip_scan_desc* table, const ts
 int tsdbhip_desc_pack(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* in, const uint32_t* order, uint32_t n,
                       tsdbhip_sg_desc* out);
 int tsdbhip_desc_pack_free(tsdbhip_ctx* ctx, tsdbhip_sg_desc* out);
+
+/* ---- the qualifier certificate of a resident descriptor (an addition to ABI v8) - */
+/*
+ * TSDBHIP_DESC_QUALS_PROVEN states, of a device descriptor: for every row with
+ * row_ncells >= 2, qualifier c of the row, read as a big-endian 16-bit word,
+ * equals q0 + c * (q1 - q0) without wrap (q0, q1: the row's first two
+ * qualifiers), and q1 - q0 is positive and a multiple of 16. That is one flags
+ * nibble for the whole row and a constant positive step in seconds, every
+ * delta at most 4095. A row of one cell is trivially proven. The statement is
+ * about the qualifier bytes alone, not about the cell type or the query.
+ *
+ * It is what the streaming kernels otherwise prove on every call by reading
+ * every qualifier (a fifth of an 8-byte row's bytes). A compacted row of a
+ * closed hour does not change between queries, so a resident table is proven
+ * once: the direct aligned group (TSDBHIP_PATH_GROUP_DIRECT) then reads only
+ * each row's fields, its first qualifier word and its values, and reports
+ * TSDBHIP_PATH_QUALS_PROVEN. What depends on the query or on the other spans
+ * (the class key, the cell width, the window, the bucket count) is still
+ * checked on every call, and a group that fails there falls back as before;
+ * the rerun from assembly proves what it reads.
+ *
+ * The flag is the caller's promise that the rows' qualifier bytes have not
+ * changed since they were proven, as TSDBHIP_DESC_DEVICE is a promise about
+ * the pointers: clear it, or certify again, when a row's bytes are rewritten
+ * or the row arrays are changed. With a false promise the results are
+ * undefined, but every access stays inside what the descriptor describes (the
+ * addresses never depend on the qualifiers not read). The flag is ignored on a
+ * host descriptor (flags without TSDBHIP_DESC_DEVICE) and by every path other
+ * than the direct aligned group; "quals_proven" "off" ignores it everywhere.
+ *
+ * tsdbhip_desc_certify reads every row's qualifiers once (one kernel, a wave a
+ * row at a time), counts the rows that fail the statement into
+ * *n_unproven_rows (may be NULL), and sets the flag in desc->flags iff the
+ * count is 0, else clears it. desc must be device resident, else
+ * TSDBHIP_E_INVALID_ARG. A row with an odd row_qual_off or with row_qual_off +
+ * 2 * row_ncells > qual_nbytes counts as unproven and none of its bytes is
+ * read: no error is raised, the query itself reports errors. Any even
+ * qualifier offset is taken. tsdbhip_last_timing: total_ms, hot_ms (the
+ * kernel), hot_kernel = TSDBHIP_HOT_DESC_CERTIFY, alg_bytes = qual_nbytes + 12
+ * B of metadata a row. A multi-device context runs the call on its first
+ * device.
+ *
+ * Producers whose buffers the context owns run the same proof on what they
+ * produced: tsdbhip_synth_generate after generation, tsdbhip_desc_pack after
+ * its copy (an input that carries the flag hands it on without a second proof:
+ * the copied bytes are the same bytes). tsdbhip_desc_gather's output carries
+ * its input's flags: a selection of proven rows is proven.
+ */
+#define TSDBHIP_HAS_DESC_CERTIFY 1
+#define TSDBHIP_HOT_DESC_CERTIFY 14   /* k_desc_certify */
+int tsdbhip_desc_certify(tsdbhip_ctx* ctx, tsdbhip_sg_desc* desc, uint64_t* n_unproven_rows);
 
 /* ---- output formatting (host cores, no GPU) ----------------------------- */
 /*

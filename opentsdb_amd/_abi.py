@@ -16,6 +16,7 @@ PATH_UNIFORM_FALLBACK = 32  # the uniform aligned group did not stand: the gener
 PATH_GROUP_DIRECT = 64  # the aligned group of one-row spans ran straight from the descriptor (no assembly)
 PATH_GROUP_DIRECT_FALLBACK = 128  # it was tried and did not stand: the call ran again from assembly
 PATH_GROUP_DIRECT_LINES = 256  # that launch read the values in whole lines (group_direct_load lines_nt)
+PATH_QUALS_PROVEN = 512  # that launch ran without the qualifier stream (DESC_QUALS_PROVEN)
 
 OK = 0
 E_ILLEGAL_DATA = -1
@@ -42,6 +43,7 @@ AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_DEV = 0, 1, 2, 3, 4
 DESC_DEVICE = 0x1
 EXACT_ORDER = 0x2
 SHARDED = 0x4
+DESC_QUALS_PROVEN = 0x8  # (device descriptors) every row's qualifiers proven regular: tsdbhip_desc_certify
 
 ROW_NONE, ROW_SINGLE, ROW_TRIVIAL, ROW_COMPLEX, ROW_ERROR, ROW_OOB = 0, 1, 2, 3, 4, 5
 
@@ -296,6 +298,8 @@ class ScanSel(C.Structure):
 
 HOT_DESC_PACK = 13
 HOT_NAMES[HOT_DESC_PACK] = "k_pack_copy"
+HOT_DESC_CERTIFY = 14
+HOT_NAMES[HOT_DESC_CERTIFY] = "k_desc_certify"
 
 
 def ptr(arr, ctype):

@@ -27,6 +27,7 @@ EXPORTS = [
     "tsdbhip_timing_totals", "tsdbhip_set_option",
     "tsdbhip_groupby_plan", "tsdbhip_desc_gather", "tsdbhip_desc_gather_free",
     "tsdbhip_find_spans", "tsdbhip_scan_rows", "tsdbhip_desc_pack", "tsdbhip_desc_pack_free",
+    "tsdbhip_desc_certify",
 ]
 
 
@@ -107,6 +108,9 @@ def lib():
     L.tsdbhip_desc_pack.restype = C.c_int
     L.tsdbhip_desc_pack_free.argtypes = [C.c_void_p, P(_abi.SgDesc)]
     L.tsdbhip_desc_pack_free.restype = C.c_int
+    if hasattr(L, "tsdbhip_desc_certify"):  # (an A/B library from before the call, TSDBHIP_LIB: calling it raises)
+        L.tsdbhip_desc_certify.argtypes = [C.c_void_p, P(_abi.SgDesc), P(C.c_uint64)]
+        L.tsdbhip_desc_certify.restype = C.c_int
     if L.tsdbhip_abi_version() != _abi.ABI_VERSION:
         raise TsdbHipError(_abi.E_INVALID_ARG, "ABI version mismatch")
     _LIB = L

@@ -1071,6 +1071,45 @@ class PackedDesc:
         return False
 
 
+# ------------------------------------------ the qualifier certificate ----
+def row_quals_proven(q):
+    """TSDBHIP_DESC_QUALS_PROVEN's statement for one row, `q` its qualifier
+    bytes: the big-endian 16-bit words are q0 + c (q1 - q0) without wrap, and
+    q1 - q0 is positive and a multiple of 16. A row of fewer than two cells is
+    proven."""
+    w = np.frombuffer(bytes(q), dtype=">u2").astype(np.int64)
+    if len(w) < 2:
+        return True
+    q0, d = int(w[0]), int(w[1]) - int(w[0])
+    if d <= 0 or d % 16 or q0 + (len(w) - 1) * d > 0xFFFF:
+        return False
+    return bool(np.array_equal(w, q0 + d * np.arange(len(w), dtype=np.int64)))
+
+
+def quals_proven(ss, qual_nbytes=None):
+    """The host restatement of tsdbhip_desc_certify over a SpanSet, row by row:
+    a bool a row, True where the row is proven. tsdbhip_desc_certify counts the
+    False ones and sets the flag iff there is none. A row at an odd offset or
+    not inside qual_nbytes (default: the buffer's length) is unproven and
+    unread."""
+    qn = len(ss.qual_bytes) if qual_nbytes is None else int(qual_nbytes)
+    ok = np.zeros(int(ss.n_rows), bool)
+    for r in range(int(ss.n_rows)):
+        qo, n = int(ss.row_qual_off[r]), int(ss.row_ncells[r])
+        if qo % 2 or qo > qn or 2 * n > qn - qo:
+            continue
+        ok[r] = row_quals_proven(ss.qual_bytes[qo:qo + 2 * n])
+    return ok
+
+
+def desc_certify(ctx, desc):
+    """One tsdbhip_desc_certify of the SgDesc `desc`: (code, n_unproven_rows);
+    desc.flags gains or loses DESC_QUALS_PROVEN."""
+    n = C.c_uint64(0)
+    rc = ctx._lib.tsdbhip_desc_certify(ctx.handle, C.byref(desc), C.byref(n))
+    return rc, int(n.value)
+
+
 # ------------------------------------------------------------ output text ----
 FMT_ASCII, FMT_GNUPLOT, FMT_CLI = 0, 1, 2
 

@@ -45,6 +45,7 @@
 #include "k_findspans.hip"
 #include "k_scanrows.hip"
 #include "k_descpack.hip"
+#include "k_desccert.hip"
 
 using namespace tsdb;
 
@@ -78,6 +79,9 @@ struct Options {
                                // device's), or a count (small test groups reach long runs with it)
   int group_direct_load = -1;  // "group_direct_load": that launch's chunk loader (reg_run's LINES): "auto" (-1:
                                // ug_direct_lines()), "rows" (0), "lines_nt" (1)
+  int quals_proven = 1;        // "quals_proven": "auto" (1: a device descriptor with TSDBHIP_DESC_QUALS_PROVEN takes
+                               // that launch's CERT instantiation, no qualifier stream), "off" (0: never), "rank0"
+                               // (2: as "auto" on rank 0 of a sharded call, "off" on the others: ranks that differ)
   int scan_rows_load = -1;     // "scan_rows_load": k_sr_match's key loader: "auto" (-1: sr_auto_lds()), "lanes" (0),
                                // "lds" (1)
   int scan_rows_blocks = 0;    // "scan_rows_blocks": that kernel's grid at most: "auto" (0: SR_BLOCKS), or a count
@@ -118,7 +122,8 @@ struct Slot {
   int8_t ev_alias[10] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // "kernel" events: a start no kernel carried reads as this one (-1: none)
   bool time_reduce = false;  // the dominant kernel is k_reduce (direct path)
   uint32_t hot_kernel = 0;
-  uint32_t gd_load_path = 0;  // TSDBHIP_PATH_GROUP_DIRECT_LINES if the call's direct launch used the whole-line loader
+  uint32_t gd_load_path = 0;  // TSDBHIP_PATH_GROUP_DIRECT_LINES if the call's direct launch used the whole-line loader,
+                              // TSDBHIP_PATH_QUALS_PROVEN if it ran without the qualifier stream
   tsdbhip_timing timing = {};
   Xchg* x = nullptr;  // the exchange of a sharded call (its rank / nranks)
   Options opt;        // the context's options, copied at the lease
@@ -604,6 +609,10 @@ extern "C" int tsdbhip_set_option(tsdbhip_ctx* ctx, const char* name, const char
     ok = false;
     for (int i = 0; i < 3; i++)
       if (v == names[i]) { o.group_direct_load = i - 1; ok = true; }
+  }
+  else if (n == "quals_proven") {
+    ok = v == "auto" || v == "off" || v == "rank0";
+    o.quals_proven = v == "off" ? 0 : (v == "auto" ? 1 : 2);
   }
   else if (n == "scan_rows_load") {
     static const char* names[] = {"auto", "lanes", "lds"};
@@ -1925,8 +1934,8 @@ DEVI void ug_fap_tail_direct(const FapArgs& fap, const UgTail& t) {
 }
 // (DIRECT: the launch with no assembly before it, ds_reg_direct_body; a
 // template argument of its own, so the other instantiations carry none of it;
-// LINES: its chunk loader, reg_run)
-template <int AGG, bool SPEC, bool DIRECT = false, bool LINES = false>
+// LINES: its chunk loader, CERT: no qualifier stream, reg_run)
+template <int AGG, bool SPEC, bool DIRECT = false, bool LINES = false, bool CERT = false>
 #ifndef UG_LDS_CAP
 #define UG_LDS_CAP 40960u  // (build knob) LDS a k_ug_ds_reg block claims: 40 KB = 4 blocks a CU
 #endif
@@ -1949,7 +1958,7 @@ k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
   }
   if constexpr (DIRECT) {
     // (the body counts its block done itself: one barrier pair per 4 runs)
-    if (ds_reg_direct_body<AGG, LINES>(a, ncells, vlen, fap, &t.sm->ug_done)) ug_fap_tail_direct(fap, t);
+    if (ds_reg_direct_body<AGG, LINES, CERT>(a, ncells, vlen, fap, &t.sm->ug_done)) ug_fap_tail_direct(fap, t);
     return;
   }
   ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
@@ -2148,12 +2157,23 @@ static uint32_t ug_direct_grid(int opt, uint32_t n_kept, uint32_t resident) {
 // ... and its chunk loader (reg_run's LINES), "group_direct_load": "auto" is the whole-line loader, which
 // measured faster at every group size tried
 static bool ug_direct_lines(int opt) { return opt != 0; }
+// ... and whether it streams the qualifiers (reg_run's CERT): not those of a device descriptor that carries
+// the certificate (tsdbhip_desc_certify), unless "quals_proven" is "off". A host descriptor's flag is ignored:
+// its bytes are the caller's to change between calls. CERT inherits the launch geometry and the loader of
+// the proving instantiations (the sweep: DESIGN.md §4).
+// Sharded, each rank decides from its own descriptor ("rank0": the ranks of an in-process sharded call, which
+// share one descriptor, made to differ); the partials, the header and the collectives are the same either way.
+static bool ug_direct_cert(const Slot* ctx, const tsdbhip_sg_desc* d, const Xchg* X) {
+  const uint32_t need = TSDBHIP_DESC_DEVICE | TSDBHIP_DESC_QUALS_PROVEN;
+  const int q = ctx->opt.quals_proven;
+  return (q == 1 || (q == 2 && X && X->rank == 0)) && (d->flags & need) == need;
+}
 // ... and the blocks of that launch resident at one time (cached: an occupancy query an instantiation, an
 // attribute query a device)
-template <int A, bool LINES>
+template <int A, bool LINES, bool CERT>
 static uint32_t ug_direct_blocks_per_cu() {
   static const uint32_t bpc = [] {
-    const void* k = (const void*)k_ug_ds_reg<A, false, true, LINES>;
+    const void* k = (const void*)k_ug_ds_reg<A, false, true, LINES, CERT>;
     hipFuncAttributes at = {};
     const unsigned stat = hipFuncGetAttributes(&at, k) == hipSuccess ? (unsigned)at.sharedSizeBytes : 21000u;
     const unsigned pad = stat < UG_LDS_CAP ? UG_LDS_CAP - stat : 0u;
@@ -2163,7 +2183,7 @@ static uint32_t ug_direct_blocks_per_cu() {
   }();
   return bpc;
 }
-static uint32_t ug_direct_resident(Slot* ctx, int ds_agg, bool lines) {
+static uint32_t ug_direct_resident(Slot* ctx, int ds_agg, bool lines, bool cert) {
   if (ctx->opt.group_direct_blocks > 0) return (uint32_t)ctx->opt.group_direct_blocks;
   static std::mutex mu;
   static std::map<int, uint32_t> cus;
@@ -2181,7 +2201,8 @@ static uint32_t ug_direct_resident(Slot* ctx, int ds_agg, bool lines) {
   }
   auto bpc = [&](auto aggc) {
     constexpr int A = decltype(aggc)::value;
-    return lines ? ug_direct_blocks_per_cu<A, true>() : ug_direct_blocks_per_cu<A, false>();
+    if (cert) return lines ? ug_direct_blocks_per_cu<A, true, true>() : ug_direct_blocks_per_cu<A, false, true>();
+    return lines ? ug_direct_blocks_per_cu<A, true, false>() : ug_direct_blocks_per_cu<A, false, false>();
   };
   switch (ds_agg) {
     case 0: return cu * bpc(std::integral_constant<int, 0>());
@@ -2248,9 +2269,10 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
     // in its last block (k_ug_ds_reg)
     // (direct: a wave takes a run of spans)
     const bool dlines = ug_direct_lines(ctx->opt.group_direct_load);
+    const bool dcert = u.direct && ug_direct_cert(ctx, d, X);
     const int drun = ctx->opt.group_direct_run;
     const uint32_t rblocks =
-        u.direct ? ug_direct_grid(drun, n_kept, drun <= 0 ? ug_direct_resident(ctx, d->ds_agg, dlines) : 0u)
+        u.direct ? ug_direct_grid(drun, n_kept, drun <= 0 ? ug_direct_resident(ctx, d->ds_agg, dlines, dcert) : 0u)
                  : (uint32_t)(((uint64_t)n_kept + 3) / 4);
     SpanDsArgs gr = {};
     gr.nseg = CK_NSEG;
@@ -2308,11 +2330,15 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
       if (u.direct) {
         const bool lines = dlines;
         if (lines) ctx->gd_load_path = TSDBHIP_PATH_GROUP_DIRECT_LINES;
+        if (dcert) ctx->gd_load_path |= TSDBHIP_PATH_QUALS_PROVEN;
         auto direct = [&](auto k) {
           LAUNCH_STOP(EV_STOP_K(ctx, 9), k, dim3(rblocks), dim3(256), pad_direct, st, u.da, gr, u.row_ncells,
                       u.row_val_len, fa, t);
         };
-        if (lines) direct(k_ug_ds_reg<A, false, true, true>);
+        // (the CERT instantiations' static LDS is the proving ones': the same arrays)
+        if (dcert && lines) direct(k_ug_ds_reg<A, false, true, true, true>);
+        else if (dcert) direct(k_ug_ds_reg<A, false, true, false, true>);
+        else if (lines) direct(k_ug_ds_reg<A, false, true, true>);
         else direct(k_ug_ds_reg<A, false, true>);
       } else if (u.spec)
         LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ug_ds_reg<A, true>), dim3(rblocks), dim3(256), pad, st, u.da, gr,
@@ -4296,6 +4322,7 @@ extern "C" int tsdbhip_spangroup_run(tsdbhip_ctx* ctx, const tsdbhip_sg_desc* de
 
 #include "batch.hip"
 #include "fmt.hip"
+#include "desccert.hip"
 
 // ------------------------------------------------- synthetic inputs ------
 // Device buffers of a generated desc are owned by ctx under keys derived from
@@ -4373,6 +4400,7 @@ extern "C" int tsdbhip_synth_generate(tsdbhip_ctx* c, const tsdbhip_synth_params
     d->qual_nbytes = n_rows * a.qstride;
     d->val_bytes = a.val;
     d->val_nbytes = n_rows * a.vstride;
+    cert_stamp(ctx, d);  // (proven as any other table is: the generator is not taken at its word)
   } catch (Fail& f) {
     return f.code;
   }

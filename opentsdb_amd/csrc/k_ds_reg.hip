@@ -631,7 +631,15 @@ DEVI int64_t ldiv64_4096(int64_t a, uint32_t n) {
 // bytes past the row's values; load_raw: 7 cells), and an instruction whose
 // whole range is past the end is skipped, a scalar branch (the 16-cell last
 // chunk of a 3600-cell row would fetch the row's last line three times more).
-template <int AGG, int W, bool LINES = false>
+//
+// CERT (the descriptor carries TSDBHIP_DESC_QUALS_PROVEN): the chunk's
+// qualifiers are neither loaded nor compared — tsdbhip_desc_certify read them
+// once and found every row the arithmetic sequence its first two cells start.
+// What is left of the proof is what each call still has to check against its
+// own query and class: the row's fields and first qualifier word (dir_fields,
+// dir_key). The value loads, their clamping and the tail are the same, so a
+// false promise changes results, never the addresses.
+template <int AGG, int W, bool LINES = false, bool CERT = false>
 DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap,
                   const RegSpan& sp, uint32_t base, uint64_t k1, uint64_t k2, const DirSpan& d0, uint32_t s,
                   uint32_t s1, uint64_t* L_v, int64_t* BK, int fop, int64_t& acc) {
@@ -697,9 +705,15 @@ DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* v
     const uint32_t c = p.c0 + 8u * lane;
     __builtin_amdgcn_s_setprio(2);
     if (!LINES) {
-      load_raw<W>(a, p.qo, p.vo, c < n ? c : (n - 1) & ~7u, x);
+      if (!CERT) {
+        load_raw<W>(a, p.qo, p.vo, c < n ? c : (n - 1) & ~7u, x);
+      } else {  // (load_raw's value loads)
+        const uint4* pv = (const uint4*)(a.val + p.vo + (uint64_t)W * (c < n ? c : (n - 1) & ~7u));
+#pragma unroll
+        for (uint32_t i = 0; i < NV; i++) x.v[i] = pv[i];
+      }
     } else {
-      x.q = *(const uint4*)(a.qual + p.qo + 2ull * (c < n ? c : (n - 1) & ~7u));
+      if (!CERT) x.q = *(const uint4*)(a.qual + p.qo + 2ull * (c < n ? c : (n - 1) & ~7u));
       const uint8_t* pv = a.val + p.vo;
       const uint32_t c0 = ufl(p.c0);
 #pragma unroll
@@ -733,13 +747,13 @@ DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* v
 #pragma unroll
       for (uint32_t i = 0; i < NV; i++) Lq[64u * i + wq] = ld.v[i];
       wave_lds_sync();
-      tr.q = ld.q;
+      if (!CERT) tr.q = ld.q;
 #pragma unroll
       for (uint32_t i = 0; i < NV; i++) tr.v[i] = Lq[NV * l + (W == 8 ? ((i + (l >> 2)) & 3u) : i)];
       if (W == 4) wave_lds_sync();
     }
     const RawW<W>& cur = LINES ? tr : ld;
-    {  // (t0 + c step - base) << 4 | flags, two cells per dword
+    if (!CERT) {  // (t0 + c step - base) << 4 | flags, two cells per dword
       const uint32_t dd = sp.t0 + (cs + 8u * lane) * sp.step - base;
       uint32_t e = ((dd << 4) | fl) * 0x00010001u + (sp.step << 20);
       const uint32_t inc = sp.step * 0x00200020u;
@@ -842,7 +856,7 @@ DEVI bool reg_run(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* v
 }
 
 // Returns true in every thread of the launch's last block to finish.
-template <int AGG, bool LINES = false>
+template <int AGG, bool LINES = false, bool CERT = false>
 DEVI bool ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const uint32_t* vlen, const FapArgs& fap,
                              uint32_t* done) {
   __shared__ uint64_t s_v[4][DCH];
@@ -879,8 +893,10 @@ DEVI bool ds_reg_direct_body(const DecodeArgs& a, const uint32_t* ncells, const 
     ok = nb <= WAVE && nb <= cap;
   }
   if (ok)
-    ok = W == 8 ? reg_run<AGG, 8, LINES>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc)
-                : reg_run<AGG, 4, LINES>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop, acc);
+    ok = W == 8 ? reg_run<AGG, 8, LINES, CERT>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop,
+                                               acc)
+                : reg_run<AGG, 4, LINES, CERT>(a, ncells, vlen, fap, sp, d.base, k1, k2, d, s, s1, s_v[wib], s_bk[wib], fop,
+                                               acc);
   if (mine && lane == 0) {  // the group's class: one key, no span outside it
     if (!ok) {
       if (!*(volatile uint32_t*)fap.broken) atomicOr(fap.broken, 1u);
