@@ -4102,9 +4102,10 @@ static int spangroup_run(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_out* ou
       rc = spangroup_run_once(ctx, d, out, a != SG_PROVEN, a == SG_FIRST || a == SG_FULL, a == SG_FIRST);
     } catch (Fail&) {
       // (an attempt that ends the call with an error has written no timing:
-      // the call's is the edges taken so far, not the call's before it)
+      // the call's is the edges taken so far and the loader of its direct launch, not
+      // the call's before it)
       ctx->timing = tsdbhip_timing{};
-      ctx->timing.paths = paths;
+      ctx->timing.paths = paths | ctx->gd_load_path;
       throw;
     }
     SgAttempt next = SG_DONE;

@@ -256,7 +256,9 @@ def test_chain_reaches_the_streaming_paths(ctx, lockstep_always, group_direct_al
                 p = tl.check(ctx, lg, AVG, False, 60, AVG, desc=out)
             finally:
                 ctx.set_option("group_direct_load", "auto")
-            tl.expect(p, tl.GD | tl.AG | tl.UNI | lines, fallbacks | (tl.GDL ^ lines), f"packed chain avg 60 {ld}")
+            # (the packer flags what it makes: the launch runs without the qualifier stream)
+            tl.expect(p, tl.GD | tl.AG | tl.UNI | lines | _abi.PATH_QUALS_PROVEN, fallbacks | (tl.GDL ^ lines),
+                      f"packed chain avg 60 {ld}")
 
 
 # ---- 4. the batch over a packed descriptor ----
