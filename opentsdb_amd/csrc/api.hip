@@ -11,6 +11,12 @@
 //   k_finalize_*      chunk combine, int/double select, NaN check   [sync 3]
 // With TSDBHIP_SHARDED the grid bitmap and the per-t partials are exchanged
 // over RCCL (allgather, then a rank-ordered combine on every rank).
+//
+// This file is host code only. The kernels are the k_*.hip parts; the three
+// included after `using namespace tsdb` stay at global scope: k_callstate.hip
+// (the call state Small and its move / publish / snapshot / end kernels),
+// k_assemble_fused.hip (assembly + kept list in one launch) and k_ug_ds_reg.hip
+// (the aligned group's finish, its tails and the hot kernel's wrapper).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h>
@@ -48,6 +54,10 @@
 #include "k_desccert.hip"
 
 using namespace tsdb;
+
+#include "k_callstate.hip"
+#include "k_assemble_fused.hip"
+#include "k_ug_ds_reg.hip"
 
 namespace {
 
@@ -97,9 +107,6 @@ struct Options {
 // each on its own stream with its own scratch (the reference's Netty workers
 // and gnuplot pool call SpanGroup concurrently, GraphHandler.java:182,285).
 struct Xchg;
-// The mapped output block's header: the call-state snapshot (Small), the
-// call's end stamp in its last word (small_snap / check_stamp)
-constexpr size_t OUT_HDR = 1024;
 
 struct Slot {
   int device = 0;
@@ -874,16 +881,35 @@ static void map_out_reserve(Slot* ctx, size_t bytes) {
   *(volatile uint64_t*)(ctx->map_out + OUT_HDR - 8) = 0;  // (no call's stamp)
 }
 
-// runtime aggregator id -> F::template run<AGG>(args...)
+// The one runtime-to-template dispatch: runtime aggregator id ->
+// f(std::integral_constant<int, K>), K in [0, N); any other id takes N - 1, so
+// N = 4 (the downsamplers of the streaming kernels: no dev) instantiates
+// nothing for aggregator 4.
+template <int N, typename F>
+static auto with_agg(int agg, F&& f) {
+  static_assert(N == 4 || N == 5, "four downsamplers, or five aggregators");
+  switch (agg) {
+    case 0: return f(std::integral_constant<int, 0>());
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    default: return f(std::integral_constant<int, N - 1>());
+  }
+}
+// ... -> F::template run<AGG>(args...)
 template <typename F, typename... A>
 static void launch_agg(int agg, A&&... args) {
-  switch (agg) {
-    case 0: F::template run<0>(args...); break;
-    case 1: F::template run<1>(args...); break;
-    case 2: F::template run<2>(args...); break;
-    case 3: F::template run<3>(args...); break;
-    default: F::template run<4>(args...); break;
-  }
+  with_agg<5>(agg, [&](auto k) { F::template run<decltype(k)::value>(args...); });
+}
+
+// a kernel's static LDS bytes, asked once a process (`fallback`: the query failed)
+template <auto KERNEL>
+static unsigned static_lds(unsigned fallback) {
+  static const unsigned bytes = [&] {
+    hipFuncAttributes at = {};
+    return hipFuncGetAttributes(&at, (const void*)KERNEL) == hipSuccess ? (unsigned)at.sharedSizeBytes : fallback;
+  }();
+  return bytes;
 }
 
 struct LaunchGeneralDs {
@@ -913,7 +939,6 @@ struct LaunchFastDsInl {
 // waves per span), then chain-proved regular-cadence spans (k_ds_spans,
 // integer, then float); leaves the spans neither took in fa.span_list for
 // k_decode_fast.
-constexpr uint32_t CK_NSEG = 64;
 // an aligned-group reduction of this call (k_ds_reg.hip FapArgs) and what its
 // rerun needs
 struct FapPlan {
@@ -960,11 +985,7 @@ struct LaunchChunks {
     // (C2) prefer the full occupancy
     // (the padding brings the block's LDS to 40 KB whatever the kernel's own
     // static LDS: a few bytes more would leave room for only 3 blocks)
-    static const unsigned stat_lds = [] {
-      hipFuncAttributes fa = {};
-      return hipFuncGetAttributes(&fa, (const void*)k_ds_reg<AGG>) == hipSuccess ? (unsigned)fa.sharedSizeBytes
-                                                                                 : 18960u;
-    }();
+    const unsigned stat_lds = static_lds<k_ds_reg<AGG>>(18960u);
     const unsigned pad = wps_log2 == 0 ? (stat_lds < 40960u ? 40960u - stat_lds : 0u) : 0u;
     // the aligned-group reduction (one wave per span): a partial row per block
     FapArgs fa0 = {};
@@ -1002,9 +1023,23 @@ struct LaunchRegRerun {
   }
 };
 
+// The finalize of f.n_chunks x f.T partials: from 64 chunks on the parallel
+// kernels (serial chunk loops are latency-bound), coalesced columns for a
+// large T; else a thread a grid point.
 template <int AGG, int MODE, bool RATE>
-static void launch_reduce(Slot* ctx, unsigned blocks, const ReduceArgs& r, const FinalArgs& f,
-                          bool par, bool finalize) {
+static void launch_finalize(Slot* ctx, const ReduceArgs& r, const FinalArgs& f) {
+  const bool par = f.n_chunks >= 64;
+  if (par && f.T >= 1024)  // (large T: coalesced columns)
+    LAUNCH((k_chunks_cols<AGG, MODE, RATE, true>), dim3((unsigned)((f.T + 63) / 64)), dim3(64 * COLW), 0,
+           ctx->stream, r, r, f, f.T, f.n_chunks);
+  else if (par)
+    LAUNCH((k_finalize_par<AGG, MODE, RATE>), dim3((unsigned)f.T), dim3(256), 0, ctx->stream, r, f);
+  else
+    LAUNCH((k_finalize_seq<AGG, MODE, RATE>), dim3(grid_for(f.T, 256)), dim3(256), 0, ctx->stream, r, f);
+}
+
+template <int AGG, int MODE, bool RATE>
+static void launch_reduce(Slot* ctx, unsigned blocks, const ReduceArgs& r, const FinalArgs& f, bool finalize) {
   if (ctx->time_reduce) EV_START(ctx, 8);
   if (r.d_info && r.chunk_e)
     LAUNCH((k_reduce<AGG, MODE, RATE, true>), dim3(blocks), dim3(256), 0, ctx->stream, r);
@@ -1015,15 +1050,7 @@ static void launch_reduce(Slot* ctx, unsigned blocks, const ReduceArgs& r, const
   else
     LAUNCH_STOP(stop, (k_reduce_w4<AGG, MODE, RATE, false>), dim3(blocks), dim3(256), lds, ctx->stream, r);
   if (ctx->time_reduce) EV_STOP_M(ctx, 9);
-  if (!finalize) return;
-  if (par && f.T >= 1024)  // (large T: coalesced columns)
-    LAUNCH((k_chunks_cols<AGG, MODE, RATE, true>), dim3((unsigned)((f.T + 63) / 64)), dim3(64 * COLW), 0,
-                       ctx->stream, r, r, f, f.T, f.n_chunks);
-  else if (par)
-    LAUNCH((k_finalize_par<AGG, MODE, RATE>), dim3((unsigned)f.T), dim3(256), 0, ctx->stream, r, f);
-  else
-    LAUNCH((k_finalize_seq<AGG, MODE, RATE>), dim3(grid_for(f.T, 256)), dim3(256), 0, ctx->stream,
-                       r, f);
+  if (finalize) launch_finalize<AGG, MODE, RATE>(ctx, r, f);
 }
 
 // k_lockstep over the group (one instantiation per value width and type; the
@@ -1044,14 +1071,7 @@ static void launch_lockstep_wf(Slot* ctx, unsigned blocks, const ReduceArgs& r, 
   EV_START(ctx, 8);
   LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_lockstep<AGG, MODE, RATE, W, FLT>), dim3(blocks), dim3(256), 0, ctx->stream, r, a);
   EV_STOP_M(ctx, 9);
-  if (!finalize) return;
-  if (f.n_chunks >= 64 && f.T >= 1024)
-    LAUNCH((k_chunks_cols<AGG, MODE, RATE, true>), dim3((unsigned)((f.T + 63) / 64)), dim3(64 * COLW), 0,
-                       ctx->stream, r, r, f, f.T, f.n_chunks);
-  else if (f.n_chunks >= 64)
-    LAUNCH((k_finalize_par<AGG, MODE, RATE>), dim3((unsigned)f.T), dim3(256), 0, ctx->stream, r, f);
-  else
-    LAUNCH((k_finalize_seq<AGG, MODE, RATE>), dim3(grid_for(f.T, 256)), dim3(256), 0, ctx->stream, r, f);
+  if (finalize) launch_finalize<AGG, MODE, RATE>(ctx, r, f);
 }
 template <int AGG>
 static void launch_lockstep(Slot* ctx, bool rate, unsigned blocks, const ReduceArgs& r, const LsPlan& p,
@@ -1068,61 +1088,35 @@ static void launch_lockstep(Slot* ctx, bool rate, unsigned blocks, const ReduceA
 }
 static void dispatch_lockstep(Slot* ctx, int agg, bool rate, unsigned blocks, const ReduceArgs& r, const LsPlan& p,
                               const FinalArgs& f, bool fin) {
-  switch (agg) {
-    case 0: return launch_lockstep<0>(ctx, rate, blocks, r, p, f, fin);
-    case 1: return launch_lockstep<1>(ctx, rate, blocks, r, p, f, fin);
-    case 2: return launch_lockstep<2>(ctx, rate, blocks, r, p, f, fin);
-    case 3: return launch_lockstep<3>(ctx, rate, blocks, r, p, f, fin);
-    default: return launch_lockstep<4>(ctx, rate, blocks, r, p, f, fin);
-  }
+  with_agg<5>(agg, [&](auto k) { launch_lockstep<decltype(k)::value>(ctx, rate, blocks, r, p, f, fin); });
 }
 
-// the uniform path's E variant: k_ug_reduce, then launch_reduce's finalize
+// the uniform path's E variant: k_ug_reduce, then the finalize
 template <int AGG, int MODE>
 static void launch_ug_reduce(Slot* ctx, const ReduceArgs& r, const FinalArgs& f) {
   const uint64_t n_waves = (r.T + WAVE - 1) / WAVE * r.n_chunks;
   LAUNCH((k_ug_reduce<AGG, MODE>), dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, ctx->stream, r);
-  if (f.n_chunks >= 64 && f.T >= 1024)
-    LAUNCH((k_chunks_cols<AGG, MODE, false, true>), dim3((unsigned)((f.T + 63) / 64)), dim3(64 * COLW), 0,
-           ctx->stream, r, r, f, f.T, f.n_chunks);
-  else if (f.n_chunks >= 64)
-    LAUNCH((k_finalize_par<AGG, MODE, false>), dim3((unsigned)f.T), dim3(256), 0, ctx->stream, r, f);
-  else
-    LAUNCH((k_finalize_seq<AGG, MODE, false>), dim3(grid_for(f.T, 256)), dim3(256), 0, ctx->stream, r, f);
-}
-template <int AGG>
-static void ug_reduce_mode(Slot* ctx, int mode, const ReduceArgs& r, const FinalArgs& f) {
-  if (mode == MODE_INT) launch_ug_reduce<AGG, MODE_INT>(ctx, r, f);
-  else launch_ug_reduce<AGG, MODE_DBL>(ctx, r, f);
+  launch_finalize<AGG, MODE, false>(ctx, r, f);
 }
 static void dispatch_ug_reduce(Slot* ctx, int agg, int mode, const ReduceArgs& r, const FinalArgs& f) {
-  switch (agg) {
-    case 0: return ug_reduce_mode<0>(ctx, mode, r, f);
-    case 1: return ug_reduce_mode<1>(ctx, mode, r, f);
-    case 2: return ug_reduce_mode<2>(ctx, mode, r, f);
-    case 3: return ug_reduce_mode<3>(ctx, mode, r, f);
-    default: return ug_reduce_mode<4>(ctx, mode, r, f);
-  }
+  with_agg<5>(agg, [&](auto k) {
+    constexpr int AGG = decltype(k)::value;
+    if (mode == MODE_INT) launch_ug_reduce<AGG, MODE_INT>(ctx, r, f);
+    else launch_ug_reduce<AGG, MODE_DBL>(ctx, r, f);
+  });
 }
 
-template <int AGG>
-static void dispatch_mode(Slot* ctx, int mode, bool rate, unsigned blocks, const ReduceArgs& r,
-                          const FinalArgs& f, bool par, bool fin) {
-  if (rate) return launch_reduce<AGG, MODE_DBL, true>(ctx, blocks, r, f, par, fin);
-  if (mode == MODE_INT) return launch_reduce<AGG, MODE_INT, false>(ctx, blocks, r, f, par, fin);
-  if (mode == MODE_DBL) return launch_reduce<AGG, MODE_DBL, false>(ctx, blocks, r, f, par, fin);
-  return launch_reduce<AGG, MODE_DUAL, false>(ctx, blocks, r, f, par, fin);
-}
-
-static void dispatch_reduce(Slot* ctx, int agg, int mode, bool rate, unsigned blocks,
-                            const ReduceArgs& r, const FinalArgs& f, bool par, bool fin) {
-  switch (agg) {
-    case 0: return dispatch_mode<0>(ctx, mode, rate, blocks, r, f, par, fin);
-    case 1: return dispatch_mode<1>(ctx, mode, rate, blocks, r, f, par, fin);
-    case 2: return dispatch_mode<2>(ctx, mode, rate, blocks, r, f, par, fin);
-    case 3: return dispatch_mode<3>(ctx, mode, rate, blocks, r, f, par, fin);
-    default: return dispatch_mode<4>(ctx, mode, rate, blocks, r, f, par, fin);
-  }
+// (the finalize's `par` is f.n_chunks >= 64: run_reduce, the one caller, sets
+// f.n_chunks to the reduce's own chunk count)
+static void dispatch_reduce(Slot* ctx, int agg, int mode, bool rate, unsigned blocks, const ReduceArgs& r,
+                            const FinalArgs& f, bool fin) {
+  with_agg<5>(agg, [&](auto k) {
+    constexpr int AGG = decltype(k)::value;
+    if (rate) return launch_reduce<AGG, MODE_DBL, true>(ctx, blocks, r, f, fin);
+    if (mode == MODE_INT) return launch_reduce<AGG, MODE_INT, false>(ctx, blocks, r, f, fin);
+    if (mode == MODE_DBL) return launch_reduce<AGG, MODE_DBL, false>(ctx, blocks, r, f, fin);
+    return launch_reduce<AGG, MODE_DUAL, false>(ctx, blocks, r, f, fin);
+  });
 }
 
 template <int AGG, int MODE>
@@ -1139,41 +1133,26 @@ static void launch_combine(Slot* ctx, const ReduceArgs& src, const ReduceArgs& d
     LAUNCH((k_combine_chunks<AGG, MODE>), dim3(grid_for(T, 256)), dim3(256), 0, ctx->stream, src,
                        dst, T, n_chunks);
 }
-template <int AGG>
-static void combine_mode(Slot* ctx, int mode, const ReduceArgs& s, const ReduceArgs& d, uint64_t T,
-                         uint32_t n) {
-  if (mode == MODE_INT) return launch_combine<AGG, MODE_INT>(ctx, s, d, T, n);
-  if (mode == MODE_DBL) return launch_combine<AGG, MODE_DBL>(ctx, s, d, T, n);
-  return launch_combine<AGG, MODE_DUAL>(ctx, s, d, T, n);
-}
 static void dispatch_combine(Slot* ctx, int agg, int mode, const ReduceArgs& s, const ReduceArgs& d,
                              uint64_t T, uint32_t n) {
-  switch (agg) {
-    case 0: return combine_mode<0>(ctx, mode, s, d, T, n);
-    case 1: return combine_mode<1>(ctx, mode, s, d, T, n);
-    case 2: return combine_mode<2>(ctx, mode, s, d, T, n);
-    case 3: return combine_mode<3>(ctx, mode, s, d, T, n);
-    default: return combine_mode<4>(ctx, mode, s, d, T, n);
-  }
+  with_agg<5>(agg, [&](auto k) {
+    constexpr int AGG = decltype(k)::value;
+    if (mode == MODE_INT) return launch_combine<AGG, MODE_INT>(ctx, s, d, T, n);
+    if (mode == MODE_DBL) return launch_combine<AGG, MODE_DBL>(ctx, s, d, T, n);
+    return launch_combine<AGG, MODE_DUAL>(ctx, s, d, T, n);
+  });
 }
 
-template <int AGG>
-static void final_mode(Slot* ctx, int mode, bool rate, const ReduceArgs& r, const FinalArgs& f) {
-  const dim3 g(grid_for(f.T, 256)), b(256);
-  if (rate) LAUNCH((k_finalize_seq<AGG, MODE_DBL, true>), g, b, 0, ctx->stream, r, f);
-  else if (mode == MODE_INT) LAUNCH((k_finalize_seq<AGG, MODE_INT, false>), g, b, 0, ctx->stream, r, f);
-  else if (mode == MODE_DBL) LAUNCH((k_finalize_seq<AGG, MODE_DBL, false>), g, b, 0, ctx->stream, r, f);
-  else LAUNCH((k_finalize_seq<AGG, MODE_DUAL, false>), g, b, 0, ctx->stream, r, f);
-}
 static void dispatch_final(Slot* ctx, int agg, int mode, bool rate, const ReduceArgs& r,
                            const FinalArgs& f) {
-  switch (agg) {
-    case 0: return final_mode<0>(ctx, mode, rate, r, f);
-    case 1: return final_mode<1>(ctx, mode, rate, r, f);
-    case 2: return final_mode<2>(ctx, mode, rate, r, f);
-    case 3: return final_mode<3>(ctx, mode, rate, r, f);
-    default: return final_mode<4>(ctx, mode, rate, r, f);
-  }
+  with_agg<5>(agg, [&](auto k) {
+    constexpr int AGG = decltype(k)::value;
+    const dim3 g(grid_for(f.T, 256)), b(256);
+    if (rate) LAUNCH((k_finalize_seq<AGG, MODE_DBL, true>), g, b, 0, ctx->stream, r, f);
+    else if (mode == MODE_INT) LAUNCH((k_finalize_seq<AGG, MODE_INT, false>), g, b, 0, ctx->stream, r, f);
+    else if (mode == MODE_DBL) LAUNCH((k_finalize_seq<AGG, MODE_DBL, false>), g, b, 0, ctx->stream, r, f);
+    else LAUNCH((k_finalize_seq<AGG, MODE_DUAL, false>), g, b, 0, ctx->stream, r, f);
+  });
 }
 
 // k_reduce launch geometry: (tile group, span chunk) per wave.
@@ -1211,64 +1190,6 @@ static ReduceGeom reduce_geom(uint64_t T, uint32_t n_kept, bool one_chunk, uint6
   return g;
 }
 
-
-// Device state of one spangroup_run call (err_raise keys, grid range, flags,
-// counters); read back at the call's host round trips.
-struct Small {
-  unsigned long long err;  // first error (err_raise key), ERR_NONE: none
-  uint32_t gflags[2];
-  uint32_t reserved;
-  unsigned long long range[2];
-  unsigned long long fstar;
-  unsigned long long n_input;
-  unsigned long long nan_t;
-  unsigned long long bad_at;
-  uint64_t n_kept;
-  uint64_t e_total;
-  uint64_t T;
-  unsigned long long bound[4];  // [min first ts, max last ts, max first ts, min last ts] of the kept spans
-  uint32_t cnt[6];  // list counters, zero at the start of a call (no memsets):
-                    // [0] assembly queue, [1] decode fallback, [2] direct list,
-                    // [3] [4] k_ds_spans int / float leftovers, [5] lockstep
-                    // proposal
-  uint32_t seg[CK_NSEG];  // k_ds_spans integer leftovers, per segment
-  uint32_t seg2[CK_NSEG];  // k_ds_reg leftovers, per segment
-  // k_ds_reg's aligned-group reduction (FAP): the spans' class keys
-  // (t0 << 32 | n, step) as [min, max, min, max], and a span outside it
-  unsigned long long fap_key[4];
-  uint32_t fap_broken, fap_done;  // (fap_done: the optimistic finish wrote the results)
-  unsigned long long fap_valid;    // this rank's aligned-group partials stand (MIN over ranks when sharded)
-  // sharded calls: two 64-bit hashes of the rank's grid bitmap (k_grid_popc /
-  // k_grid_scan_blocks), and the agreed header words of the one collective
-  // after the local grids (XH_*: MIN, or complemented MAX, over the ranks)
-  unsigned long long ghash[2];
-  // the lockstep proposal (k_direct_opt): class keys [min, max, min, max];
-  // ls_broken: k_lockstep found a qualifier off the proposal (MAX over ranks)
-  unsigned long long ls_key[4];
-  uint32_t ls_broken, ls_pad;
-  unsigned long long xh[14];  // (XH_N, + the aligned-group validity in an optimistic call)
-  // the uniform-group proposal (assembly): the kept spans' class keys
-  // (x0 << 32 | n, step << 32 | q0) as [min, max, min, max]; a span that
-  // proposes none holds ~0 in the first word
-  unsigned long long ukey[4];
-  uint32_t ug_done;   // k_ug_ds_reg's blocks done (its last block runs the tail)
-  uint32_t ug_tried;  // (speculative k_ug_ds_reg) the group was attempted
-  uint32_t ug_go;     // (speculative) ug_spec_fits() of the kept spans, by the kept-list kernel
-  uint32_t ug_pad2;
-};
-// Small.xh slots of the grid-agreement header. Every rank decides from these
-// agreed words alone (never from its own lo / hi against them), so the ranks
-// take the same branch: the grids agree iff min lo == max lo, min hi == max
-// hi and both hashes are equal everywhere (the hashes are over word indices
-// relative to each rank's own lo; equal lo makes them comparable)
-enum { XH_ERR = 0, XH_GF0, XH_GF1, XH_FSTAR, XH_LO, XH_HI, XH_H1MIN, XH_H1MAX, XH_H2MIN, XH_H2MAX, XH_LOMAX, XH_HIMIN, XH_N };
-
-// the agreement test on the agreed header (identical on every rank)
-__host__ __device__ inline bool xh_grids_agree(const unsigned long long* xh) {
-  return xh[XH_LO] == ~xh[XH_LOMAX] && ~xh[XH_HI] == xh[XH_HIMIN] && xh[XH_H1MIN] == ~xh[XH_H1MAX] &&
-         xh[XH_H2MIN] == ~xh[XH_H2MAX];
-}
-
 static Small small_init() {
   Small init = {};
   init.err = ERR_NONE;
@@ -1304,51 +1225,10 @@ static const Small* small_init_dev(Slot* ctx) {
 // 3 immediate MIN, 4 immediate MAX, 5 u64 field MIN, 6 u64 field MAX (left in
 // the packed buffer only)
 struct XField { void* p; uint8_t kind; uint64_t imm; };
-constexpr uint32_t XM_MAX = 14;
 struct XExtra { void* p; uint64_t count; XType t; XOp op; };
-static void xchg_minmax(Slot* ctx, Xchg* X, const XField* f, uint32_t n, uint64_t* sum_u64 = nullptr,
-                        uint64_t* buf = nullptr, const XExtra* extra = nullptr, uint32_t n_extra = 0);
 // sharded double partials exchange rank-owned slices of G from this |G| on
 // (below it, one allgather of every rank's partials is the cheaper collective)
 constexpr uint64_t XSLICE_MIN_T = 65536;
-static_assert(sizeof(Small) <= OUT_HDR - 8, "Small and the call's stamp must fit the output header");
-
-// End of a call, after the finalize: the call state is snapshot ahead of the
-// outputs (one D2H copy brings both back) and reset for the next call; the
-// words of the grid points are cleared, which leaves the bitmap zero.
-// Packing of small call-state fields for one MIN allreduce (a MAX field
-// travels complemented): one thread moves up to 8 words in or out of a
-// contiguous u64 buffer. kinds: 0 u64, 1 ~u64, 2 ~u32 (to u64); out: the same
-// inverses.
-struct XMove {
-  uint32_t n;
-  uint8_t kind[XM_MAX];
-  uint64_t* buf;          // [n] the packed words
-  void* field[XM_MAX];    // the call-state fields
-  uint64_t imm[XM_MAX];   // kinds 3 / 4
-  int32_t out;            // 0: fields -> buf, 1: buf -> fields
-};
-DEVI void xmove_one(const XMove& m, uint32_t i) {
-  const uint8_t k = m.kind[i];
-  const bool cpl = k == 1 || k == 2 || k == 4 || k == 6;  // MAX kinds travel complemented
-  if (!m.out) {
-    const uint64_t v = k == 2 ? (uint64_t)*(const uint32_t*)m.field[i]
-                       : (k == 3 || k == 4) ? m.imm[i] : *(const uint64_t*)m.field[i];
-    m.buf[i] = cpl ? ~v : v;
-  } else if (k <= 2) {
-    const uint64_t v = cpl ? ~m.buf[i] : m.buf[i];
-    if (k == 2) *(uint32_t*)m.field[i] = (uint32_t)v;
-    else *(uint64_t*)m.field[i] = v;
-  }
-}
-DEVI void xmove_run(const XMove& m) {
-  for (uint32_t i = 0; i < m.n; i++) xmove_one(m, i);
-}
-// a thread a field (one thread walking them paid a dependent round trip each:
-// 6.7 us for the 12-field header)
-__global__ void __launch_bounds__(64) k_xmove(XMove m) {
-  if (threadIdx.x < m.n) xmove_one(m, threadIdx.x);
-}
 
 // (sum_u64: one more field, a u64 SUM, in the same collective group. The
 // pack / unpack kernels stay outside the group: RCCL issues a group's
@@ -1369,617 +1249,13 @@ static void xchg_group(Slot* ctx, Xchg* X, const XMove& m, uint64_t* sum_u64, co
   for (uint32_t i = 0; i < n_extra; i++) X->allreduce(ctx, extra[i].p, extra[i].count, extra[i].t, extra[i].op);
   X->group_end(ctx);
 }
-static void xchg_minmax(Slot* ctx, Xchg* X, const XField* f, uint32_t n, uint64_t* sum_u64, uint64_t* buf,
-                        const XExtra* extra, uint32_t n_extra) {
-  XMove m = {};
-  m.n = n;
-  m.buf = buf ? buf : scratch<uint64_t>(ctx, "x_pack", XM_MAX);
-  for (uint32_t i = 0; i < n; i++) { m.kind[i] = f[i].kind; m.field[i] = f[i].p; m.imm[i] = f[i].imm; }
+static void xchg_minmax(Slot* ctx, Xchg* X, const XField* f, uint32_t n, uint64_t* sum_u64 = nullptr,
+                        uint64_t* buf = nullptr, const XExtra* extra = nullptr, uint32_t n_extra = 0) {
+  XMove m = xchg_desc(ctx, f, n, buf);
   LAUNCH(k_xmove, dim3(1), dim3(64), 0, ctx->stream, m);
-  X->group_start(ctx);
-  X->allreduce(ctx, m.buf, n, X_U64, X_MIN);
-  if (sum_u64) X->allreduce(ctx, sum_u64, 1, X_U64, X_SUM);
-  for (uint32_t i = 0; i < n_extra; i++) X->allreduce(ctx, extra[i].p, extra[i].count, extra[i].t, extra[i].op);
-  X->group_end(ctx);
+  xchg_group(ctx, X, m, sum_u64, extra, n_extra);
   m.out = 1;
   LAUNCH(k_xmove, dim3(1), dim3(64), 0, ctx->stream, m);
-}
-
-// dst (global geometry [dst_lo, ...]) = src (a rank's bitmap over [src_lo,
-// ...], src_lo >= dst_lo) shifted into place; bits outside src read as 0.
-__global__ void __launch_bounds__(256) k_bitmap_remap(const uint32_t* src, uint64_t src_words, int64_t src_lo,
-                                                      uint32_t* dst, uint64_t dst_words, int64_t dst_lo) {
-  const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (w >= dst_words) return;
-  const int64_t sb = (int64_t)(32 * w) - (src_lo - dst_lo);  // src bit of dst bit 32 w
-  const int64_t i0 = sb >= 0 ? sb / 32 : -((31 - sb) / 32);   // floor(sb / 32)
-  const uint32_t sh = (uint32_t)(sb - 32 * i0);
-  auto at = [&](int64_t i) { return i >= 0 && (uint64_t)i < src_words ? src[i] : 0u; };
-  const uint32_t a = at(i0), b = at(i0 + 1);
-  dst[w] = sh ? (a >> sh) | (b << (32 - sh)) : a;
-}
-
-// The call state to the host (host_publish) after a producer that could not
-// publish it itself (a multi-block kernel, a collective).
-__global__ void __launch_bounds__(64) k_publish(HostPub pub, const uint64_t* src) { host_publish(pub, src); }
-
-// Groups of up to 1024 spans: the assembly (thread per span, then the
-// deferred spans a wave each) and the kept-list compaction in one 1024-thread
-// block, one launch instead of three.
-__global__ void __launch_bounds__(1024) k_assemble_small(AssembleArgs a, KeptArgs K) {
-  __shared__ uint32_t s_list[1024];
-  __shared__ uint32_t s_n;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) s_n = 0;
-  __syncthreads();
-  if (t < a.n_spans && assemble_fast_one(a, t)) s_list[atomicAdd(&s_n, 1u)] = t;
-  __syncthreads();
-  const uint32_t nd = s_n;
-  for (uint32_t w = t / WAVE; w < nd; w += 1024 / WAVE) assemble_span_wave(a, s_list[w]);
-  __syncthreads();  // (the block's global writes visible to the whole block)
-  kept_compact_block(K);
-}
-
-// Groups of (nearly) single-row spans beyond one block (rows <= 2 x spans:
-// C3's 1M series): a tile of 256 spans assembled (a thread a span, the
-// block's waves walking the deferred ones, as k_assemble_small) and its kept
-// sums in one launch, instead of k_assemble_fast, k_assemble and
-// k_kept_tiles. The sums of the tile travel as one wave-reduced row per wave
-// through LDS (one barrier).
-__global__ void __launch_bounds__(256) k_assemble_tiles(AssembleArgs a, KeptTile* tile_sum, ulonglong2* tile_ke) {
-  __shared__ uint32_t s_list[256];
-  __shared__ uint32_t s_n;
-  __shared__ uint64_t s_r[4][11];
-  const uint32_t t = threadIdx.x, lane = lane_id(), w = t / WAVE;
-  const uint32_t s = blockIdx.x * 256 + t;
-  if (t == 0) s_n = 0;
-  __syncthreads();
-  if (s < a.n_spans && assemble_fast_one(a, s)) s_list[atomicAdd(&s_n, 1u)] = s;
-  __syncthreads();
-  const uint32_t nd = s_n;
-  for (uint32_t i = w; i < nd; i += 256 / WAVE) assemble_span_wave(a, s_list[i]);
-  if (nd) __syncthreads();  // (the block's global writes visible to the whole block)
-  uint64_t sk = 0, se = 0, cnt = 0;
-  int64_t f = INT64_MAX, l = INT64_MIN, fx = INT64_MIN, ln = INT64_MAX;
-  UKeyAcc u;
-  u.init();
-  if (s < a.n_spans) {
-    se = a.sp_cap[s];
-    if (a.sp_kept[s]) {
-      sk = 1;
-      cnt = a.sp_ncells[s];
-      f = fx = a.sp_first[s];
-      l = ln = a.sp_last[s];
-      if (a.u_key1) u.add(a.u_key1[s], a.u_key2[s]);
-    }
-  }
-#pragma unroll
-  for (int m = 1; m < WAVE; m <<= 1) {
-    sk += shfl_xor_u64(sk, m);
-    se += shfl_xor_u64(se, m);
-    cnt += shfl_xor_u64(cnt, m);
-    f = min(f, (int64_t)shfl_xor_u64((uint64_t)f, m));
-    l = max(l, (int64_t)shfl_xor_u64((uint64_t)l, m));
-    fx = max(fx, (int64_t)shfl_xor_u64((uint64_t)fx, m));
-    ln = min(ln, (int64_t)shfl_xor_u64((uint64_t)ln, m));
-  }
-  if (a.u_key1) u.wave_reduce();
-  if (lane == 0) {
-    uint64_t* r = s_r[w];
-    r[0] = sk; r[1] = se; r[2] = cnt; r[3] = (uint64_t)f; r[4] = (uint64_t)l; r[5] = (uint64_t)fx; r[6] = (uint64_t)ln;
-    r[7] = u.a0; r[8] = u.a1; r[9] = u.b0; r[10] = u.b1;
-  }
-  __syncthreads();
-  if (t == 0) {
-    for (int i = 1; i < 4; i++) {
-      const uint64_t* r = s_r[i];
-      sk += r[0]; se += r[1]; cnt += r[2];
-      f = min(f, (int64_t)r[3]); l = max(l, (int64_t)r[4]); fx = max(fx, (int64_t)r[5]); ln = min(ln, (int64_t)r[6]);
-      u.a0 = min(u.a0, r[7]); u.a1 = max(u.a1, r[8]); u.b0 = min(u.b0, r[9]); u.b1 = max(u.b1, r[10]);
-    }
-    KeptTile o;
-    o.k = sk; o.e = se; o.cnt = cnt; o.pad = 0;
-    o.f = cnt ? f : INT64_MAX; o.l = cnt ? l : INT64_MIN; o.fx = cnt ? fx : INT64_MIN; o.ln = cnt ? ln : INT64_MAX;
-    o.u = u;
-    tile_sum[blockIdx.x] = o;
-    tile_ke[blockIdx.x] = make_ulonglong2(sk, se);
-  }
-}
-
-// Small unsharded calls also compute the lazy error index here (block 0,
-// before the snapshot; bad.n_kept = 0: k_bad_index ran).
-// (the optimistic aligned-group finish: `done` null, or the call is over only
-// when *done; otherwise the state is snapshot for the host and left as it is)
-// The call state's snapshot into mapped host memory and, with `init`, its
-// reset: word by word over the block's threads, every thread of the block
-// calling (one thread copying the ~1 KB across PCIe took most of a 10-12 us
-// single-block launch)
-static_assert(sizeof(Small) % 8 == 0, "Small is copied in 8-byte words");
-// The call's stamp (the word after the snapshot, OUT_HDR - 8): the call's
-// sequence number, stored last by thread 0 with a system-scope release once
-// every thread's snapshot words are fenced. Every host-visible result of the
-// call was written before it: the finalize's small results into the same
-// mapped block and the reduce's long results into registered caller buffers
-// by kernels that completed earlier in the stream, the aligned-group finish's
-// results by this block before the fence. The host checks the stamp before it
-// reads any of them (check_stamp).
-DEVI void small_snap(Small* sm, Small* snap, const Small* init, uint64_t seq) {
-  constexpr uint32_t NW = sizeof(Small) / 8;
-  const volatile uint64_t* s = (const volatile uint64_t*)sm;
-  uint64_t* d = (uint64_t*)snap;
-  for (uint32_t i = threadIdx.x; i < NW; i += blockDim.x) d[i] = s[i];
-  __threadfence_system();  // (the snapshot's host writes complete before this kernel does)
-  __syncthreads();  // (every word read and fenced before any is reset, and before the stamp)
-  if (threadIdx.x == 0)
-    __hip_atomic_store((uint64_t*)((uint8_t*)snap + OUT_HDR - 8), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (!init) return;
-  const uint64_t* in = (const uint64_t*)init;
-  uint64_t* w = (uint64_t*)sm;
-  for (uint32_t i = threadIdx.x; i < NW; i += blockDim.x) w[i] = in[i];
-}
-__global__ void __launch_bounds__(256) k_call_end(Small* sm, Small* snap, const Small* init, uint32_t* bitmap,
-                                                  const uint32_t* grid, uint64_t T, int64_t lo, BadArgs bad,
-                                                  uint64_t seq, const uint32_t* done = nullptr) {
-  __shared__ unsigned long long s_min[4];
-  if (done) {
-    __shared__ uint64_t s_t;
-    __shared__ uint32_t s_over;
-    if (threadIdx.x == 0) {
-      s_over = *(volatile const uint32_t*)done;
-      s_t = sm->T;
-    }
-    __syncthreads();
-    if (!s_over) {
-      if (blockIdx.x == 0) small_snap(sm, snap, nullptr, seq);
-      return;
-    }
-    T = s_t;
-  }
-  if (blockIdx.x == 0) {
-    if (bad.n_kept) {
-      unsigned long long m = ~0ull;
-      for (uint32_t k = threadIdx.x; k < bad.n_kept; k += 256) m = min(m, (unsigned long long)bad_key(bad, k));
-      for (int o = 1; o < WAVE; o <<= 1) m = min(m, (unsigned long long)shfl_xor_u64(m, o));
-      if (lane_id() == 0) s_min[threadIdx.x / WAVE] = m;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        m = min(min(s_min[0], s_min[1]), min(s_min[2], s_min[3]));
-        if (m != ~0ull) atomicMin(&sm->bad_at, m);
-        __threadfence();
-      }
-    }
-    __syncthreads();  // (bad_at final)
-    small_snap(sm, snap, init, seq);
-    __syncthreads();  // (the ranks above read the bitmap cleared below)
-  }
-  if (bitmap)
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (uint64_t)gridDim.x * 256)
-      bitmap[(uint64_t)((int64_t)grid[i] - lo) >> 5] = 0u;
-}
-
-// ---- the optimistic aligned-group finish (no host round trip after the
-// grid when the group turns out aligned; see spangroup_run) ----
-// this rank's partials stand: every kept span in the one class, G its bucket
-// sequence of at most 64 points, no float, no error
-// (one thread; then, sharded, the agreement header packed for the group)
-// (a whole wave: lane i packs field i; the validity is this wave's own value,
-// not re-read from the call state)
-DEVI void fap_valid_pack(Small* sm, uint32_t fap_ran, const XMove& pack, uint64_t T) {
-  const bool v = fap_ran && sm->err == ERR_NONE && !sm->fap_broken && sm->fap_key[0] == sm->fap_key[1] &&
-                 sm->fap_key[2] == sm->fap_key[3] && T > 0 && T <= WAVE && sm->gflags[0] == 0;
-  const uint32_t lane = lane_id();
-  if (lane == 0) sm->fap_valid = v ? 1ull : 0ull;
-  if (lane < pack.n) {
-    if (pack.field[lane] == (void*)&sm->fap_valid) pack.buf[lane] = v ? 1ull : 0ull;  // (kind 0: MIN, as is)
-    else xmove_one(pack, lane);
-  }
-}
-// this rank's 64-slot partials (k_fap_final64's reduce), its validity, the pack
-template <int OP>
-__global__ void __launch_bounds__(1024) k_fap_final64v(const int64_t* tmp, uint32_t n, uint32_t n_kept, int64_t* p_i,
-                                                       uint32_t* p_cnt, Small* sm, XMove pack) {
-  __shared__ int64_t s[16][WAVE];
-  const int lane = lane_id();
-  const uint32_t w = threadIdx.x / WAVE;
-  int64_t acc = fap_rows_wave<OP>(tmp, w, 16, n);
-  acc = fap_block_comb<OP>(acc, s);
-  if (w == 0) {
-    const uint64_t T = *(volatile const uint64_t*)&sm->T;
-    const bool in = (uint64_t)lane < T;
-    p_i[lane] = in ? acc : fap_neutral(OP);
-    p_cnt[lane] = in ? n_kept : 0u;
-    fap_valid_pack(sm, 1u, pack, T);
-  }
-}
-// a rank without an aligned-group attempt: neutral partials for the exchange
-__global__ void k_fap_neutral64(int64_t* p_i, uint32_t* p_cnt, int op, Small* sm, XMove pack) {
-  p_i[threadIdx.x] = fap_neutral(op);
-  p_cnt[threadIdx.x] = 0;
-  fap_valid_pack(sm, 0u, pack, 0);
-}
-// The finalize of the (exchanged) 64-slot partials when the group stands
-// everywhere (sharded: and every rank's grid is the global one; outputs at a
-// fixed stride of 64: ts | bits | is_int), then k_call_end's `done` variant,
-// in one block of 256 threads: the call state is snapshot, and reset with
-// the bitmap cleared iff the group stood
-template <int AGG>
-__global__ void __launch_bounds__(256) k_fap_finish_end(Small* sm, const int64_t* p_i, const uint32_t* p_cnt,
-                                                        FinalArgs f, int32_t sharded, XMove unpack, Small* snap,
-                                                        const Small* init, uint32_t* bitmap, const uint32_t* grid, int64_t lo,
-                                                        uint64_t seq) {
-  __shared__ uint32_t s_ok, s_T;
-  const uint32_t t = threadIdx.x;
-  if (t < unpack.n) xmove_one(unpack, t);  // the agreed header back into the call state (sharded), a field a thread
-  __syncthreads();
-  if (t == 0) {
-    bool ok = sm->fap_valid != 0 && sm->err == ERR_NONE && sm->gflags[0] == 0 && sm->T > 0 && sm->T <= WAVE;
-    // (sharded: rank-independent: an empty grid anywhere makes lo's MIN / MAX
-    // differ, ~0 vs a real lo; all empty fails T > 0 on every rank)
-    if (sharded) ok = ok && xh_grids_agree(sm->xh);
-    s_ok = ok ? 1u : 0u;
-    s_T = (uint32_t)sm->T;
-  }
-  __syncthreads();
-  if (!s_ok) {  // the group did not stand: the state stays for the usual path
-    small_snap(sm, snap, nullptr, seq);
-    return;
-  }
-  if (t < s_T) {
-    Acc a;
-    acc_init(a);
-    a.cnt = p_cnt[t];
-    a.ia = p_i[t];
-    finalize_one<AGG, MODE_INT, false>(f, t, a);
-  }
-  __syncthreads();
-  if (t == 0) sm->fap_done = 1;
-  __syncthreads();
-  small_snap(sm, snap, init, seq);
-  __syncthreads();  // (the grid read below is this block's own)
-  if (bitmap && t < s_T) bitmap[(uint64_t)((int64_t)grid[t] - lo) >> 5] = 0u;
-}
-
-// ---- the uniform path's aligned group in one launch (uniform_run) ----
-// k_ds_reg's body with each block's 64 bucket partials combined by device
-// atomics into one of `ncopy` copies (neutral on entry), then the tail in the
-// launch's last block (the blocks count themselves done on Small.ug_done
-// after their atomics are acknowledged): the copies combined (and reset), G
-// from the class key (bucket b of every span: t0 + b kk step +
-// floor(step (m_b - 1) / 2) over its m_b cells, Span.java:377-422), the
-// group's validity; unsharded, also k_fap_finish_end's finish (the results
-// into mapped host memory, the state snapshot + reset + stamp); sharded, the
-// 64-slot partials and the agreement header for the exchange, the finish
-// after it. One launch for k_ds_reg + k_fap_rows + k_fap_final64v
-// (+ k_fap_finish_end).
-constexpr uint32_t UG_NCOPY = 16;  // (4 a thread of the tail, loaded together)
-__global__ void k_fill_u64(unsigned long long* p, uint32_t n, unsigned long long v) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v;
-}
-struct UgTail {
-  Small* sm;
-  int op;        // the block combine (0 wrapping add, 1 min, 2 max)
-  int agg;       // the cross-series aggregator (finalize)
-  int32_t sharded;
-  uint32_t n_kept, t0, step, kk, ncell, nb;
-  uint32_t* grid;    // G (<= 64 points)
-  int64_t* p_i;      // (sharded) the 64-slot partials for the exchange
-  uint32_t* p_cnt;
-  XMove pack;        // (sharded) the agreement header
-  FinalArgs fo;      // (unsharded) the results into mapped host memory
-  Small* snap;
-  const Small* init;
-  uint64_t seq;
-  // (speculative, unsharded: the key, n_kept, kk and nb come from the call
-  // state; a group that is not one leaves the state as the host would find it)
-  uint32_t spec;
-  int64_t interval;
-};
-template <typename T>
-DEVI T coherent_load(const T* p) {  // (past any stale L2 line: the other blocks wrote by atomics)
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the tail of the launch the host sized (the key, n_kept, kk and nb in UgTail)
-DEVI void ug_fap_tail(const FapArgs& fap, const UgTail& t) {
-  __shared__ int64_t s_acc[4][WAVE];
-  const uint32_t tid = threadIdx.x, lane = tid % WAVE, w = tid / WAVE;
-  const int op = t.op;
-  const int64_t neutral = fap_neutral(op);
-  auto comb = [&](int64_t x, int64_t y) { return op == 0 ? ladd(x, y) : (op == 1 ? min(x, y) : max(x, y)); };
-  int64_t acc = neutral;
-  {  // (coherent loads, all in flight together; the copies reset to neutral after)
-    int64_t v[UG_NCOPY / 4];
-#pragma unroll
-    for (uint32_t i = 0; i < UG_NCOPY / 4; i++)
-      v[i] = (int64_t)coherent_load(fap.copies + (uint64_t)(w + 4 * i) * WAVE + lane);
-#pragma unroll
-    for (uint32_t i = 0; i < UG_NCOPY / 4; i++) {
-      acc = comb(acc, v[i]);
-      fap.copies[(uint64_t)(w + 4 * i) * WAVE + lane] = (unsigned long long)neutral;
-    }
-  }
-  s_acc[w][lane] = acc;
-  __syncthreads();
-  Small* sm = t.sm;
-  __shared__ uint32_t s_ok;
-  if (w == 0) {
-    acc = comb(comb(s_acc[0][lane], s_acc[1][lane]), comb(s_acc[2][lane], s_acc[3][lane]));
-    const bool in = lane < t.nb;
-    if (in) {
-      const uint32_t sb = lane * t.kk, m = min(sb + t.kk, t.ncell) - sb;
-      t.grid[lane] = t.t0 + sb * t.step + (uint32_t)((uint64_t)t.step * (m - 1) / 2);
-    }
-    const bool v = coherent_load(&sm->err) == ERR_NONE && !coherent_load(&sm->fap_broken) &&
-                   coherent_load(&sm->fap_key[0]) == coherent_load(&sm->fap_key[1]) &&
-                   coherent_load(&sm->fap_key[2]) == coherent_load(&sm->fap_key[3]) && t.nb > 0 && t.nb <= WAVE &&
-                   coherent_load(&sm->gflags[0]) == 0;
-    if (lane == 0) {
-      sm->T = t.nb;
-      sm->fap_valid = v ? 1ull : 0ull;
-      s_ok = v ? 1u : 0u;
-    }
-    if (t.sharded) {
-      t.p_i[lane] = in ? acc : neutral;
-      t.p_cnt[lane] = in ? t.n_kept : 0u;
-      if (lane < t.pack.n) {
-        if (t.pack.field[lane] == (void*)&sm->fap_valid) t.pack.buf[lane] = v ? 1ull : 0ull;
-        else xmove_one(t.pack, lane);
-      }
-    } else if (v && in) {
-      Acc a;
-      acc_init(a);
-      a.cnt = t.n_kept;
-      a.ia = acc;
-      switch (t.agg) {
-        case 1: finalize_one<1, MODE_INT, false>(t.fo, lane, a); break;
-        case 2: finalize_one<2, MODE_INT, false>(t.fo, lane, a); break;
-        case 3: finalize_one<3, MODE_INT, false>(t.fo, lane, a); break;
-        default: finalize_one<0, MODE_INT, false>(t.fo, lane, a); break;
-      }
-    }
-  }
-  __syncthreads();
-  if (t.sharded) return;
-  // the finish: the results written, the state snapshot and, when the group
-  // stood, reset (the host reads fap_done; else the general path runs)
-  if (s_ok && tid == 0) sm->fap_done = 1;
-  __syncthreads();
-  small_snap(sm, t.snap, s_ok ? t.init : nullptr, t.seq);
-}
-// the speculative launch's tail (sharded): the verdict, key and counts from
-// the call state
-DEVI void ug_fap_tail_spec(const FapArgs& fap, const UgTail& t) {
-  __shared__ int64_t s_acc[4][WAVE];
-  const uint32_t tid = threadIdx.x, lane = tid % WAVE, w = tid / WAVE;
-  // (the key's fields as locals: a copy of the UgTail, whose pack arrays are
-  // indexed by lane, put the whole struct in scratch — 928 B a lane, the
-  // launch 3x slower)
-  uint32_t n_kept = t.n_kept, t0 = t.t0, step = t.step, kk0 = t.kk, ncell = t.ncell, nbk = t.nb;
-  bool fits = true;
-  if (t.spec) {
-    Small* sm = t.sm;
-    uint32_t nb = 0, kk = 0;
-    fits = sm->ug_go != 0;
-    ug_spec_fits(sm->ukey[0], sm->ukey[1], sm->ukey[2], sm->ukey[3], sm->n_kept, sm->err, t.interval, &nb, &kk);
-    // (not one: this rank's partials neutral, its validity 0, as
-    // k_fap_neutral64's; the exchange is every rank's)
-    n_kept = fits ? (uint32_t)sm->n_kept : 0u;
-    t0 = (uint32_t)(sm->ukey[0] >> 32);
-    ncell = (uint32_t)sm->ukey[0];
-    step = (uint32_t)(sm->ukey[2] >> 32);
-    kk0 = fits ? kk : 1u;
-    nbk = fits ? nb : 0u;
-    if (tid == 0) sm->ug_tried = 1;
-  }
-  const int op = t.op;
-  const int64_t neutral = fap_neutral(op);
-  auto comb = [&](int64_t x, int64_t y) { return op == 0 ? ladd(x, y) : (op == 1 ? min(x, y) : max(x, y)); };
-  int64_t acc = neutral;
-  {  // (coherent loads, all in flight together; the copies reset to neutral after)
-    int64_t v[UG_NCOPY / 4];
-#pragma unroll
-    for (uint32_t i = 0; i < UG_NCOPY / 4; i++)
-      v[i] = (int64_t)coherent_load(fap.copies + (uint64_t)(w + 4 * i) * WAVE + lane);
-#pragma unroll
-    for (uint32_t i = 0; i < UG_NCOPY / 4; i++) {
-      acc = comb(acc, v[i]);
-      fap.copies[(uint64_t)(w + 4 * i) * WAVE + lane] = (unsigned long long)neutral;
-    }
-  }
-  s_acc[w][lane] = acc;
-  __syncthreads();
-  Small* sm = t.sm;
-  __shared__ uint32_t s_ok;
-  if (w == 0) {
-    acc = comb(comb(s_acc[0][lane], s_acc[1][lane]), comb(s_acc[2][lane], s_acc[3][lane]));
-    const bool in = lane < nbk;
-    if (in) {
-      const uint32_t sb = lane * kk0, m = min(sb + kk0, ncell) - sb;
-      t.grid[lane] = t0 + sb * step + (uint32_t)((uint64_t)step * (m - 1) / 2);
-    }
-    const bool v = coherent_load(&sm->err) == ERR_NONE && !coherent_load(&sm->fap_broken) &&
-                   coherent_load(&sm->fap_key[0]) == coherent_load(&sm->fap_key[1]) &&
-                   coherent_load(&sm->fap_key[2]) == coherent_load(&sm->fap_key[3]) && nbk > 0 && nbk <= WAVE &&
-                   coherent_load(&sm->gflags[0]) == 0;
-    if (lane == 0) {
-      sm->T = nbk;
-      sm->fap_valid = v ? 1ull : 0ull;
-      s_ok = v ? 1u : 0u;
-    }
-    if (t.sharded) {
-      t.p_i[lane] = in ? acc : neutral;
-      t.p_cnt[lane] = in ? n_kept : 0u;
-      if (lane < t.pack.n) {
-        if (t.pack.field[lane] == (void*)&sm->fap_valid) {
-          t.pack.buf[lane] = v ? 1ull : 0ull;
-        } else if (t.spec && (lane == 4 || lane == 5 || lane == 10 || lane == 11)) {
-          // (speculative: the class key's header words, uniform_run's fx[4, 5,
-          // 10, 11], from the device key — ~0 / 0 for a rank without a group)
-          const uint64_t a1 = fits ? sm->ukey[0] : ~0ull, a2 = fits ? sm->ukey[2] : 0ull;
-          const uint64_t val = (lane == 4 || lane == 10) ? a1 : a2;
-          t.pack.buf[lane] = t.pack.kind[lane] == 4 ? ~val : val;
-        } else {
-          xmove_one(t.pack, lane);
-        }
-      }
-    } else if (v && in) {
-      Acc a;
-      acc_init(a);
-      a.cnt = n_kept;
-      a.ia = acc;
-      switch (t.agg) {
-        case 1: finalize_one<1, MODE_INT, false>(t.fo, lane, a); break;
-        case 2: finalize_one<2, MODE_INT, false>(t.fo, lane, a); break;
-        case 3: finalize_one<3, MODE_INT, false>(t.fo, lane, a); break;
-        default: finalize_one<0, MODE_INT, false>(t.fo, lane, a); break;
-      }
-    }
-  }
-  __syncthreads();
-  if (t.sharded) return;
-  // the finish: the results written, the state snapshot and, when the group
-  // stood, reset (the host reads fap_done; else the general path runs)
-  if (s_ok && tid == 0) sm->fap_done = 1;
-  __syncthreads();
-  small_snap(sm, t.snap, s_ok ? t.init : nullptr, t.seq);
-}
-// the direct launch's tail (ds_reg_direct_body: no assembly ran): the class
-// key, the verdict, kk and nb from the call state's fap_key; what assembly and
-// the kept list would have published (every span kept: n_kept, n_input) is
-// written here when the group is one. A sibling of ug_fap_tail_spec, not a
-// mode of it or of ug_fap_tail (see k_ug_ds_reg on folding tails).
-DEVI void ug_fap_tail_direct(const FapArgs& fap, const UgTail& t) {
-  __shared__ int64_t s_acc[4][WAVE];
-  const uint32_t tid = threadIdx.x, lane = tid % WAVE, w = tid / WAVE;
-  Small* sm = t.sm;
-  const unsigned long long k1 = coherent_load(&sm->fap_key[0]), k2 = coherent_load(&sm->fap_key[2]);
-  // (one class, every span in it; else this rank's partials neutral and its
-  // validity 0, as k_fap_neutral64's)
-  const bool one = !coherent_load(&sm->fap_broken) && k1 == coherent_load(&sm->fap_key[1]) &&
-                   k2 == coherent_load(&sm->fap_key[3]) && (k2 >> 32) != 0;
-  const uint32_t t0 = (uint32_t)(k1 >> 32), ncell = (uint32_t)k1, step = (uint32_t)(k2 >> 32);
-  const uint32_t n_kept = one ? t.n_kept : 0u;
-  const uint32_t kk0 = one ? (uint32_t)((t.interval + step - 1) / step) : 1u;
-  const uint32_t nbk = one ? (ncell + kk0 - 1) / kk0 : 0u;
-  const int op = t.op;
-  const int64_t neutral = fap_neutral(op);
-  auto comb = [&](int64_t x, int64_t y) { return op == 0 ? ladd(x, y) : (op == 1 ? min(x, y) : max(x, y)); };
-  int64_t acc = neutral;
-  {  // (coherent loads, all in flight together; the copies reset to neutral after)
-    int64_t v[UG_NCOPY / 4];
-#pragma unroll
-    for (uint32_t i = 0; i < UG_NCOPY / 4; i++)
-      v[i] = (int64_t)coherent_load(fap.copies + (uint64_t)(w + 4 * i) * WAVE + lane);
-#pragma unroll
-    for (uint32_t i = 0; i < UG_NCOPY / 4; i++) {
-      acc = comb(acc, v[i]);
-      fap.copies[(uint64_t)(w + 4 * i) * WAVE + lane] = (unsigned long long)neutral;
-    }
-  }
-  s_acc[w][lane] = acc;
-  __syncthreads();
-  __shared__ uint32_t s_ok;
-  if (w == 0) {
-    acc = comb(comb(s_acc[0][lane], s_acc[1][lane]), comb(s_acc[2][lane], s_acc[3][lane]));
-    const bool in = lane < nbk;
-    if (in) {
-      const uint32_t sb = lane * kk0, m = min(sb + kk0, ncell) - sb;
-      t.grid[lane] = t0 + sb * step + (uint32_t)((uint64_t)step * (m - 1) / 2);
-    }
-    const bool v = one && coherent_load(&sm->err) == ERR_NONE && nbk > 0 && nbk <= WAVE &&
-                   coherent_load(&sm->gflags[0]) == 0;
-    if (lane == 0) {
-      sm->T = nbk;
-      sm->fap_valid = v ? 1ull : 0ull;
-      s_ok = v ? 1u : 0u;
-      if (one) {  // (the kept-list kernel's counts: every span kept, n cells each)
-        sm->n_kept = n_kept;
-        sm->n_input = (unsigned long long)n_kept * ncell;
-      }
-    }
-    if (t.sharded) {
-      t.p_i[lane] = in ? acc : neutral;
-      t.p_cnt[lane] = in ? n_kept : 0u;
-      if (lane < t.pack.n) {
-        if (t.pack.field[lane] == (void*)&sm->fap_valid) {
-          t.pack.buf[lane] = v ? 1ull : 0ull;
-        } else if (lane == 4 || lane == 5 || lane == 10 || lane == 11) {
-          // (the class key's header words, as the speculative tail's: ~0 / 0
-          // for a rank without a group)
-          const uint64_t a1 = one ? k1 : ~0ull, a2 = one ? k2 : 0ull;
-          const uint64_t val = (lane == 4 || lane == 10) ? a1 : a2;
-          t.pack.buf[lane] = t.pack.kind[lane] == 4 ? ~val : val;
-        } else {
-          xmove_one(t.pack, lane);
-        }
-      }
-    } else if (v && in) {
-      Acc a;
-      acc_init(a);
-      a.cnt = n_kept;
-      a.ia = acc;
-      switch (t.agg) {
-        case 1: finalize_one<1, MODE_INT, false>(t.fo, lane, a); break;
-        case 2: finalize_one<2, MODE_INT, false>(t.fo, lane, a); break;
-        case 3: finalize_one<3, MODE_INT, false>(t.fo, lane, a); break;
-        default: finalize_one<0, MODE_INT, false>(t.fo, lane, a); break;
-      }
-    }
-  }
-  __syncthreads();
-  if (t.sharded) return;
-  // the finish, as ug_fap_tail's
-  if (s_ok && tid == 0) sm->fap_done = 1;
-  __syncthreads();
-  small_snap(sm, t.snap, s_ok ? t.init : nullptr, t.seq);
-}
-// (DIRECT: the launch with no assembly before it, ds_reg_direct_body; a
-// template argument of its own, so the other instantiations carry none of it;
-// LINES: its chunk loader, CERT: no qualifier stream, reg_run)
-template <int AGG, bool SPEC, bool DIRECT = false, bool LINES = false, bool CERT = false>
-#ifndef UG_LDS_CAP
-#define UG_LDS_CAP 40960u  // (build knob) LDS a k_ug_ds_reg block claims: 40 KB = 4 blocks a CU
-#endif
-#ifndef UG_WPE
-#define UG_WPE 0  // (build knob) waves per SIMD the register allocation aims at, 0: the compiler's choice
-#endif
-__global__ void __launch_bounds__(256)
-#if UG_WPE
-__attribute__((amdgpu_waves_per_eu(UG_WPE, UG_WPE)))
-#endif
-k_ug_ds_reg(DecodeArgs a, SpanDsArgs g, const uint32_t* ncells,
-                                                   const uint32_t* vlen, FapArgs fap, UgTail t) {
-  extern __shared__ uint8_t s_pad[];
-  if (threadIdx.x == 0 && a.n_kept == 0xFFFFFFFFu) s_pad[0] = 1;
-  if (SPEC && !sld(&t.sm->ug_go)) {
-    // (speculative, no group: every block leaves at once — no counter; the
-    // sharded tail, which packs this rank's neutral share, runs in block 0)
-    if (t.sharded && blockIdx.x == 0) ug_fap_tail_spec(fap, t);
-    return;
-  }
-  if constexpr (DIRECT) {
-    // (the body counts its block done itself: one barrier pair per 4 runs)
-    if (ds_reg_direct_body<AGG, LINES, CERT>(a, ncells, vlen, fap, &t.sm->ug_done)) ug_fap_tail_direct(fap, t);
-    return;
-  }
-  ds_reg_body<AGG, SPEC>(a, g, ncells, vlen, 0u, fap);
-  __shared__ uint32_t s_last;
-  __builtin_amdgcn_s_waitcnt(0);  // (this wave's atomics acknowledged)
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(&t.sm->ug_done, 1u) == gridDim.x - 1 ? 1u : 0u;
-  __syncthreads();
-  if (!s_last) return;
-  // (two tails: the host-sized one is the code the unsharded C3* launch was
-  // measured with — folding the speculative logic into it cost that launch
-  // ~2.5 %, same box, through the whole kernel's code generation)
-  if (SPEC) ug_fap_tail_spec(fap, t);
-  else ug_fap_tail(fap, t);
-}
-
-// TSDBHIP_CHECK_CLEAN: counts non-zero words of a buffer (debug of the
-// zero-on-entry invariants)
-__global__ void k_count_nonzero(const uint32_t* p, uint64_t n, unsigned long long* out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256)
-    if (p[i]) atomicAdd(out, 1ull);
 }
 
 // The device address of a host buffer registered mapped (tsdbhip_host_register)
@@ -2173,12 +1449,11 @@ static bool ug_direct_cert(const Slot* ctx, const tsdbhip_sg_desc* d, const Xchg
 template <int A, bool LINES, bool CERT>
 static uint32_t ug_direct_blocks_per_cu() {
   static const uint32_t bpc = [] {
-    const void* k = (const void*)k_ug_ds_reg<A, false, true, LINES, CERT>;
-    hipFuncAttributes at = {};
-    const unsigned stat = hipFuncGetAttributes(&at, k) == hipSuccess ? (unsigned)at.sharedSizeBytes : 21000u;
+    constexpr auto k = k_ug_ds_reg<A, false, true, LINES, CERT>;
+    const unsigned stat = static_lds<k>(21000u);
     const unsigned pad = stat < UG_LDS_CAP ? UG_LDS_CAP - stat : 0u;
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 256, pad) != hipSuccess || nb < 1) nb = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k, 256, pad) != hipSuccess || nb < 1) nb = 1;
     return (uint32_t)nb;
   }();
   return bpc;
@@ -2199,17 +1474,11 @@ static uint32_t ug_direct_resident(Slot* ctx, int ds_agg, bool lines, bool cert)
     }
     cu = c;
   }
-  auto bpc = [&](auto aggc) {
+  return cu * with_agg<4>(ds_agg, [&](auto aggc) {
     constexpr int A = decltype(aggc)::value;
     if (cert) return lines ? ug_direct_blocks_per_cu<A, true, true>() : ug_direct_blocks_per_cu<A, false, true>();
     return lines ? ug_direct_blocks_per_cu<A, true, false>() : ug_direct_blocks_per_cu<A, false, false>();
-  };
-  switch (ds_agg) {
-    case 0: return cu * bpc(std::integral_constant<int, 0>());
-    case 1: return cu * bpc(std::integral_constant<int, 1>());
-    case 2: return cu * bpc(std::integral_constant<int, 2>());
-    default: return cu * bpc(std::integral_constant<int, 3>());
-  }
+  });
 }
 
 // the aligned group (k_ug_ds_reg; sharded: one collective group and
@@ -2308,22 +1577,12 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
     t.seq = end_seq;
     t.spec = u.spec ? 1u : 0u;
     t.interval = I;
-    auto reg = [&](auto aggc) {
+    with_agg<4>(d->ds_agg, [&](auto aggc) {
       constexpr int A = decltype(aggc)::value;
-      static const unsigned stat_lds = [] {
-        hipFuncAttributes at = {};
-        return hipFuncGetAttributes(&at, (const void*)k_ug_ds_reg<A, false>) == hipSuccess
-                   ? (unsigned)at.sharedSizeBytes
-                   : 21000u;
-      }();
+      const unsigned stat_lds = static_lds<k_ug_ds_reg<A, false>>(21000u);
       // (the direct instantiation's own static LDS: the block claims exactly UG_LDS_CAP; the
       // loaders share it, the whole-line one transposes in place)
-      static const unsigned stat_lds_direct = [] {
-        hipFuncAttributes at = {};
-        return hipFuncGetAttributes(&at, (const void*)k_ug_ds_reg<A, false, true>) == hipSuccess
-                   ? (unsigned)at.sharedSizeBytes
-                   : 21000u;
-      }();
+      const unsigned stat_lds_direct = static_lds<k_ug_ds_reg<A, false, true>>(21000u);
       const unsigned pad = stat_lds < UG_LDS_CAP ? UG_LDS_CAP - stat_lds : 0u;
       const unsigned pad_direct = stat_lds_direct < UG_LDS_CAP ? UG_LDS_CAP - stat_lds_direct : 0u;
       EV_START(ctx, 8);
@@ -2347,13 +1606,7 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
         LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ug_ds_reg<A, false>), dim3(rblocks), dim3(256), pad, st, u.da, gr,
                     u.row_ncells, u.row_val_len, fa, t);
       EV_STOP_M(ctx, 9);
-    };
-    switch (d->ds_agg) {
-      case 0: reg(std::integral_constant<int, 0>()); break;
-      case 1: reg(std::integral_constant<int, 1>()); break;
-      case 2: reg(std::integral_constant<int, 2>()); break;
-      default: reg(std::integral_constant<int, 3>()); break;
-    }
+    });
     ctx->hot_kernel = TSDBHIP_HOT_UG_DS_REG;
   }
   if (sharded) {
@@ -2362,15 +1615,12 @@ static int ug_aligned_group(Slot* ctx, const UgIn& u, tsdbhip_sg_out* out, tsdbh
     const XExtra ex[2] = {{o_pi, WAVE, fop ? X_I64 : X_U64, fop == 1 ? X_MIN : (fop == 2 ? X_MAX : X_SUM)},
                           {o_pc, WAVE, X_U32, X_SUM}};
     xchg_group(ctx, X, pack, (uint64_t*)&sm->n_input, ex, 2);
-    auto fin = [&](auto aggc) {
+    // (the aligned group's queries hold agg <= 3: ug_fap_q, group_direct_q)
+    with_agg<4>(agg, [&](auto aggc) {
       constexpr int A = decltype(aggc)::value;
       LAUNCH(k_fap_finish_end<A>, dim3(1), dim3(256), 0, st, sm, (const int64_t*)o_pi, (const uint32_t*)o_pc, fo,
              (int32_t)1, unpack, snap, ini, (uint32_t*)nullptr, (const uint32_t*)gridv, (int64_t)0, end_seq);
-    };
-    if (agg == TSDBHIP_AGG_MIN) fin(std::integral_constant<int, 1>());
-    else if (agg == TSDBHIP_AGG_MAX) fin(std::integral_constant<int, 2>());
-    else if (agg == TSDBHIP_AGG_AVG) fin(std::integral_constant<int, 3>());
-    else fin(std::integral_constant<int, 0>());
+    });
   }
   EV_FINAL(ctx, 5);
   HIPCHK(hipStreamSynchronize(st));
@@ -2436,8 +1686,7 @@ static void ug_e_launch(Slot* ctx, const UgIn& u, uint64_t T, uint32_t e_kk, int
   // (waves a span, its rows in contiguous pieces: C2's 24 rows a span, 0.266
   // ms a step with 3 pieces, 0.269 with 2, 0.281 with 4, 0.290 with 1,
   // 0.310 with 8, 0.489 with 24 — same box)
-  uint32_t pieces = ug_e_pieces(x0, step, n, e_kk, (uint32_t)std::max<uint64_t>(1, rps / 8));
-  if (const char* e = getenv("TSDBHIP_UG_P")) pieces = (uint32_t)std::max(1, atoi(e));  // (A/B runs)
+  const uint32_t pieces = ug_e_pieces(x0, step, n, e_kk, (uint32_t)std::max<uint64_t>(1, rps / 8));
   const uint32_t rblocks = (uint32_t)(((uint64_t)n_kept * pieces + 3) / 4);
   SpanDsArgs gr = {};
   gr.nseg = CK_NSEG;
@@ -2446,25 +1695,15 @@ static void ug_e_launch(Slot* ctx, const UgIn& u, uint64_t T, uint32_t e_kk, int
   fa.broken = &sm->ls_broken;
   fa.ug_grid = gridv;
   fa.ug_t0 = x0; fa.ug_step = step; fa.ug_kk = e_kk; fa.ug_n = n; fa.ug_pieces = pieces;
-  auto reg = [&](auto aggc) {
+  with_agg<4>(d->ds_agg, [&](auto aggc) {
     constexpr int A = decltype(aggc)::value;
-    static const unsigned stat_lds = [] {
-      hipFuncAttributes at = {};
-      return hipFuncGetAttributes(&at, (const void*)k_ds_reg<A>) == hipSuccess ? (unsigned)at.sharedSizeBytes
-                                                                               : 18960u;
-    }();
+    const unsigned stat_lds = static_lds<k_ds_reg<A>>(18960u);
     const unsigned pad = pieces == 1 ? (stat_lds < 40960u ? 40960u - stat_lds : 0u) : 0u;
     EV_START(ctx, 8);
     LAUNCH_STOP(EV_STOP_K(ctx, 9), (k_ds_reg<A>), dim3(rblocks), dim3(256), pad, st, u.da, gr, u.row_ncells,
                 u.row_val_len, wps_log2, fa);
     EV_STOP_M(ctx, 9);
-  };
-  switch (d->ds_agg) {
-    case 0: reg(std::integral_constant<int, 0>()); break;
-    case 1: reg(std::integral_constant<int, 1>()); break;
-    case 2: reg(std::integral_constant<int, 2>()); break;
-    default: reg(std::integral_constant<int, 3>()); break;
-  }
+  });
   // (integer dev: one span-ordered chunk, Aggregators.java:196-217; else
   // chunks of 64 spans, merged in chunk order by the finalize)
   const bool seq = agg == TSDBHIP_AGG_DEV && mode != MODE_DBL;
@@ -3350,7 +2589,6 @@ struct SgCall {
     // |G| below. A decode error leaves every e_len <= its capacity, so the grid
     // kernels stay inside E before the error is thrown.)
 
-
     // the optimistic aligned-group finish (below): unsharded, when this group
     // was tried as one; sharded, for every query that allows the attempt (all
     // ranks must issue the same collectives)
@@ -3467,14 +2705,10 @@ struct SgCall {
         Small* snap = (Small*)ctx->map_out_dev;
         const Small* ini = small_init_dev(ctx);
         const uint64_t seq = end_seq;
-        if (agg == TSDBHIP_AGG_MIN)
-          LAUNCH(k_fap_finish_end<1>, dim3(1), dim3(256), 0, st, sm, (const int64_t*)o_pi, (const uint32_t*)o_pc, fo, (int32_t)sharded, um, snap, ini, bitmap, (const uint32_t*)gridv_o, lo, seq);
-        else if (agg == TSDBHIP_AGG_MAX)
-          LAUNCH(k_fap_finish_end<2>, dim3(1), dim3(256), 0, st, sm, (const int64_t*)o_pi, (const uint32_t*)o_pc, fo, (int32_t)sharded, um, snap, ini, bitmap, (const uint32_t*)gridv_o, lo, seq);
-        else if (agg == TSDBHIP_AGG_AVG)
-          LAUNCH(k_fap_finish_end<3>, dim3(1), dim3(256), 0, st, sm, (const int64_t*)o_pi, (const uint32_t*)o_pc, fo, (int32_t)sharded, um, snap, ini, bitmap, (const uint32_t*)gridv_o, lo, seq);
-        else
-          LAUNCH(k_fap_finish_end<0>, dim3(1), dim3(256), 0, st, sm, (const int64_t*)o_pi, (const uint32_t*)o_pc, fo, (int32_t)sharded, um, snap, ini, bitmap, (const uint32_t*)gridv_o, lo, seq);
+        with_agg<4>(agg, [&](auto aggc) {  // (fap_opt holds agg <= 3: fap_query, the plan of fap_ran)
+          LAUNCH(k_fap_finish_end<decltype(aggc)::value>, dim3(1), dim3(256), 0, st, sm, (const int64_t*)o_pi,
+                 (const uint32_t*)o_pc, fo, (int32_t)sharded, um, snap, ini, bitmap, (const uint32_t*)gridv_o, lo, seq);
+        });
       }
       EV_FINAL(ctx, 5);
       HIPCHK(hipStreamSynchronize(st));
@@ -3759,7 +2993,7 @@ struct SgCall {
     FinalArgs f = fin;
     f.n_chunks = n_chunks;
     const unsigned blocks = (unsigned)((n_waves + 3) / 4);
-    dispatch_reduce(ctx, agg, mode, rate, blocks, r, f, n_chunks >= 64, finalize);
+    dispatch_reduce(ctx, agg, mode, rate, blocks, r, f, finalize);
     return r;
   }
 
@@ -4049,7 +3283,6 @@ static int spangroup_run_once(Slot* ctx, const tsdbhip_sg_desc* d, tsdbhip_sg_ou
   return c.run();
 }
 
-
 // The call's attempts and their rerun edges, in one place. An attempt is
 // spangroup_run_once with the proposals it may try; an attempt that returns
 // a rerun code hands the call to the attempt its edge names (every rank of a
@@ -4333,7 +3566,6 @@ static std::string synth_key(const tsdbhip_sg_desc* d, const char* f) {
   snprintf(b, sizeof b, "syn%p_%s", (const void*)d, f);
   return b;
 }
-
 
 extern "C" int tsdbhip_synth_generate(tsdbhip_ctx* c, const tsdbhip_synth_params* p, tsdbhip_sg_desc* d) {
   if (!c || !p || !d || p->n_spans == 0 || p->n_points == 0 || p->step == 0 || 3600 % p->step ||

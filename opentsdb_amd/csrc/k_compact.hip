@@ -772,9 +772,6 @@ DEVI int cq_row_lds(const CompactArgs& a, uint64_t r, const RowHdr& h, const Row
       *ncells_out = ncells;
       return -1;
     }
-#ifdef CR_ABL
-    if (CR_ABL & 2) st = CQ_ERROR; else
-#endif
     st = cq_complex_lds<SORT>(L, p, nk, nvalid - nmulti, ncells, keys, pay, runs, lane, &oql, &ovl);
     reached = CQ_REACHED_COMPLEX;
   } else if (!any_fix && !any_junk) {
@@ -1085,9 +1082,6 @@ DEVI void cq_unstage_wave(uint8_t* dst, const uint8_t* lds, uint32_t i0, uint64_
 #ifndef CR_WPE
 #define CR_WPE 5        // waves per SIMD the register allocation aims at (the compiler's 119 VGPRs; 5: -0.02 ms, 6: none)
 #endif
-#ifndef CR_ABL
-#define CR_ABL 0        // (ablation builds only, wrong results: 1 no write/delete decision, 2 no complexCompact)
-#endif
 static_assert(CW_SORT % WAVE == 0 && (CW_SORT & (CW_SORT - 1)) == 0, "in-wave sort size");
 struct __attribute__((aligned(16))) CrLds {
   uint8_t qlen[2 * CR_KCAP + 32];
@@ -1182,7 +1176,7 @@ DEVI void cr_row(const CompactArgs& a, CrLds& L, const RowHdr& h, uint64_t r, ui
   wave_lds_sync();
   if (st & CQ_REACHED_COMPLEX) {
     (*n_cx)++;
-    if ((st & 0xFF) == CQ_COMPLEX && a.out_write && !(CR_ABL & 1))
+    if ((st & 0xFF) == CQ_COMPLEX && a.out_write)
       cq_dup_core(
           a, r, h.nk, h.qs, h.vs, oql, ovl, L.qin + p.qo, L.vout + p.vo,
           [&](uint64_t k) { return lds_u16(L.qlen, p.k0 + 2 * (uint32_t)k); },
@@ -1294,9 +1288,6 @@ k_compact_rows(CompactArgs a) {
 #ifndef CW_WPE
 #define CW_WPE 7       // waves per SIMD the register allocation aims at (C5 call, same box: the compiler's 80 VGPRs 0.898 ms, 7: 0.856, 8: 0.956)
 #endif
-#ifndef CW_ABL
-#define CW_ABL 0       // (ablation builds only, wrong results: 2 no value output, 4 no plain test)
-#endif
 constexpr uint32_t CW_KPT = CW_KCAP / WAVE;  // KVs a lane
 static_assert(CW_KPT == 4 || CW_KPT == 8, "k_compact_wave: 4 or 8 KVs a lane");
 static_assert(CW_ROWS >= 1 && CW_ROWS < WAVE, "k_compact_wave: rows a run");
@@ -1378,7 +1369,7 @@ DEVI void cw_piece(const CompactArgs& a, CwLds& L, uint64_t r0, uint32_t j0, uin
   wave_lds_sync();
   // ---- 2. the plain test, flat over the KVs: CW_KPT consecutive KVs a lane ----
   const uint32_t kb = CW_KPT * t;
-  const bool any = kb < NK && !(CW_ABL & 4);
+  const bool any = kb < NK;
   uint32_t ir[CW_KPT], q_[CW_KPT], ql_[CW_KPT], vl_[CW_KPT], c_[CW_KPT], pre_[CW_KPT];
   uint32_t fm = 0, lm = 0;  // bit u: KV kb + u is its row's first / last
   uint32_t sum = 0;
@@ -1519,7 +1510,7 @@ DEVI void cw_piece(const CompactArgs& a, CwLds& L, uint64_t r0, uint32_t j0, uin
       }
       return lo;
     };
-    for (uintptr_t c = c0 + 16ull * t; c < c1 && !(CW_ABL & 2); c += 16ull * WAVE) {
+    for (uintptr_t c = c0 + 16ull * t; c < c1; c += 16ull * WAVE) {
       const uint32_t i = find(c - ov_abs);
       CvRow n = {};
       if (i + 1 < np) n = L.w[i + 1];

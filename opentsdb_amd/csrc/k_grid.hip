@@ -351,7 +351,7 @@ DEVI uint32_t grid_rank2(const uint32_t* bitmap, const uint32_t* word_rank, cons
   return word_rank[w] + block_sum[w >> 10] + __popc(bitmap[w] & ((1u << (b & 31)) - 1));
 }
 
-// End of a single-group call (api.hip), after the finalize: every set bit of
+// End of a single-group call (k_call_end, k_callstate.hip), after the finalize: every set bit of
 // the bitmap is a grid point, so clearing the word of each grid point leaves
 // the whole bitmap zero for the next call (no memset per call).
 __global__ void __launch_bounds__(256) k_bitmap_clear(uint32_t* bitmap, const uint32_t* grid, uint64_t T, int64_t lo) {

@@ -300,9 +300,6 @@ __global__ void __launch_bounds__(256) k_lockstep(ReduceArgs r, LockstepArgs L) 
 #define UG_DEV_NP 4u  // producer waves (the block: 2 + UG_DEV_NP waves; C3 1M series 2 / 4: 39.8 / 39.2 ms)
 #endif
 constexpr uint32_t DEV_B = UG_DEV_B;  // spans a phase
-#ifndef UG_DEV_ABL
-#define UG_DEV_ABL 0
-#endif
 template <uint32_t W, uint32_t GP>
 __global__ void __launch_bounds__(64 * (2 + UG_DEV_NP)) k_ug_dev(const uint8_t* val, const uint64_t* vo, const uint8_t* qual,
                                                const uint64_t* qo, uint32_t q0, uint32_t* broken, uint32_t n_kept,
@@ -344,7 +341,6 @@ __global__ void __launch_bounds__(64 * (2 + UG_DEV_NP)) k_ug_dev(const uint8_t* 
   DevSet sa, sb, sc, sd;
   auto slot = [&](uint32_t i) { return (w - 2) * SPL + NP * SPL * i + si; };  // span slot of the phase
   auto load_offs = [&](DevSet& S, uint32_t ph) {  // (spans past the last: the last one's, never stored)
-    if (UG_DEV_ABL == 2) return;
 #pragma unroll
     for (uint32_t i = 0; i < PER; i++) {
       const uint32_t k = min(ph * DEV_B + slot(i), n_kept - 1);
@@ -353,10 +349,6 @@ __global__ void __launch_bounds__(64 * (2 + UG_DEV_NP)) k_ug_dev(const uint8_t* 
     }
   };
   auto load_vals = [&](DevSet& S) {
-    if (UG_DEV_ABL == 2) {
-      for (uint32_t i = 0; i < PER; i++) { S.v[i] = (int64_t)i; S.q[i] = qexp; }
-      return;
-    }
 #pragma unroll
     for (uint32_t i = 0; i < PER; i++) {
       const uint8_t* p = val + S.ov[i] + (uint64_t)W * gc;
@@ -408,7 +400,7 @@ __global__ void __launch_bounds__(64 * (2 + UG_DEV_NP)) k_ug_dev(const uint8_t* 
       if (ph + AH < nph) store(ph + AH, cur);
       if (ph + AH + D < nph) load_vals(cur);
       if (ph + AH + 2 * D < nph) load_offs(cur, ph + AH + 2 * D);
-    } else if (w == 0 && ph < nph && (uint32_t)lane < GP && UG_DEV_ABL != 5) {  // the mean chains
+    } else if (w == 0 && ph < nph && (uint32_t)lane < GP) {  // the mean chains
       // (span 0 takes the same step from mean = 0 with n = 1: d = x, q = x
       // exactly, mean' = x — wf_push's first value — so no step is special)
       const uint32_t nk = min(DEV_B, n_kept - ph * DEV_B), b3 = ph % RB, b2 = ph & 1;
@@ -417,15 +409,8 @@ __global__ void __launch_bounds__(64 * (2 + UG_DEV_NP)) k_ug_dev(const uint8_t* 
         const double dn = (double)(base + j);  // (exact: n < 2^32)
         const double d = x - mean;
         const double qa = d * r;
-#if UG_DEV_ABL == 1  // (ablation builds only, wrong results: 1 the product without its correction,
-                    // 2 no loads, 3 a one-add chain, 4 no M2 sums, 5 no mean chain)
-        const double nm = mean + qa;
-#elif UG_DEV_ABL == 3
-        const double nm = mean + x;
-#else
         const double e = __builtin_fma(-dn, qa, d);
         const double nm = mean + __builtin_fma(e, r, qa);
-#endif
         s_dm[b2][j][lane] = make_double2(d, nm);
         mean = nm;
       };
@@ -461,7 +446,7 @@ __global__ void __launch_bounds__(64 * (2 + UG_DEV_NP)) k_ug_dev(const uint8_t* 
       } else {  // the last, partial phase
         for (uint32_t j = 0; j < nk; j++) chain_step(j, s_buf[b3][j][lane], s_rcp[b3][j]);
       }
-    } else if (w == 1 && ph >= 1 && (uint32_t)lane < GP && UG_DEV_ABL != 4) {  // the M2 sums of the phase before
+    } else if (w == 1 && ph >= 1 && (uint32_t)lane < GP) {  // the M2 sums of the phase before
       const uint32_t p = ph - 1, nk = min(DEV_B, n_kept - p * DEV_B), b3 = p % RB, b2 = p & 1;
       for (uint32_t j = p == 0 ? 1u : 0u; j < nk; j++) {
         const double2 dm = s_dm[b2][j][lane];

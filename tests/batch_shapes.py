@@ -22,13 +22,13 @@ MODE_INT, MODE_DBL, MODE_DUAL = 0, 1, 2  # k_reduce.hip:27
 SUM, MIN, MAX, AVG, DEV = 0, 1, 2, 3, 4
 
 # ---- constants of the batch's host geometry, copied -------------------------
-TARGET_WAVES = 16384   # batch.hip:421 (reduce_geom's target, api.hip:1145, times the group's share)
-MIN_WAVES = 2048       # batch.hip:422 (reduce_geom's min_waves, api.hip:1146, times the share)
+TARGET_WAVES = 16384   # batch.hip:421 (reduce_geom's target, api.hip, times the group's share)
+MIN_WAVES = 2048       # batch.hip:422 (reduce_geom's min_waves, api.hip, times the share)
 TARGET_FLOOR = 64      # batch.hip:421 (max(64, ...))
 MIN_WAVES_FLOOR = 16   # batch.hip:422 (max(16, ...))
-TILE = 64              # api.hip:1148 (grid points a tile: one wave)
-CHUNK_SPANS = 256      # api.hip:1156 (chunks of ~256 spans)
-CHUNK_MIN_SPANS = 16   # api.hip:1158 (no chunk below 16 spans)
+TILE = 64              # api.hip: reduce_geom's n_tiles (grid points a tile: one wave)
+CHUNK_SPANS = 256      # api.hip: reduce_geom's by_size (chunks of ~256 spans)
+CHUNK_MIN_SPANS = 16   # api.hip: reduce_geom's want (no chunk below 16 spans)
 RANK_BLOCK = 1024      # batch.hip:328 (bitmap words a rank block; k_group.hip:192 block_sum[w >> 10])
 SCAN_BLOCKS = 256      # k_grid_scan_blocks: rank blocks a round (batch.hip:342, one block of 256 threads)
 STATS_BLOCKS = 65536   # batch.hip:193,330 (blocks of k_group_stats / k_group_words; they stride beyond)
@@ -186,7 +186,7 @@ class Build:
 
 # ---- the restatement of spangroup_run_batch's host geometry -------------------
 def reduce_geom(T, nk, one_chunk, target, min_waves):
-    """api.hip:1145-1170 (no spc_cap: the batch passes none): (spc, n_chunks, tpw, ntg, n_waves)"""
+    """api.hip: reduce_geom (no spc_cap: the batch passes none): (spc, n_chunks, tpw, ntg, n_waves)"""
     n_tiles = (T + TILE - 1) // TILE
     if one_chunk or nk == 0:
         n_chunks, spc = 1, max(nk, 1)

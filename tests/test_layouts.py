@@ -37,7 +37,7 @@ None of them looks at the order of the rows or at the bytes between them.
                                       else         -                   UNI LS GD REDONE UFB
   1 auto, downsampling                streamable   UNI iff packed's    LS GD REDONE UFB
                                       proposable   UFB iff packed's    UNI LS GD DR GDF
-                                                   UNI (k_ug_ds_reg declines at :293 / :404: api.hip:3978-3980)
+                                                   UNI (k_ug_ds_reg declines at :293 / :404: api.hip, kSgEdges' RC_UG_FALLBACK edges)
                                       else         -                   UNI UFB LS GD REDONE
   2 lockstep=always, not dev          proposable   UNI LS              REDONE
     integer dev without rate          proposable   UNI                 LS REDONE
@@ -46,7 +46,7 @@ None of them looks at the order of the rows or at the bytes between them.
   3 aligned group                     streamable   AG, UNI iff !exact  AR GD REDONE
                                       proposable   AR, UFB iff !exact  AG UNI GD GDF DR
                                       else         AR                  AG UNI UFB GD GDF DR
-    (AR: the general k_ds_reg's members fail reg_rows_ok, the group is broken, api.hip:3542-3545)
+    (AR: the general k_ds_reg's members fail reg_rows_ok, the group is broken, api.hip: SgCall::plan_reduce's fap_use)
   4 group_direct=always               streamable   GD AG UNI, GDL iff  GDF UFB AR
                                                    lines_nt
                                       proposable   GDF UFB AR, GDL     GD AG UNI DR
@@ -55,9 +55,9 @@ None of them looks at the order of the rows or at the bytes between them.
   6 ranks: no downsampling as 2 (dev: the span-ordered pass, no bit); integers in 60-s buckets:
                                       streamable   UNI AG              AR GD REDONE
                                       else         UFB AR              AG UNI GD GDF DR
-    (every rank of a sharded call makes the uniform attempt, api.hip:3062, so a group that does not stand falls back)
+    (every rank of a sharded call makes the uniform attempt, api.hip: SgCall::uniform_try, so a group that does not stand falls back)
     exact                             all          -                   UNI LS GD AG AR REDONE
-    (no aligned group on a sharded exact call, api.hip:2997)
+    (no aligned group on a sharded exact call, api.hip: SgCall::plan)
   7 device descriptors                as the host descriptor's row above
   8 the chain (compact_rows' layout)  as `compact`
 
@@ -435,8 +435,8 @@ def test_ranks(mctx, pool, kind, name):
                 expect(p, UNI | LS, GD | REDONE, q)
             if agg == DEV or (flt and not exact):
                 continue
-            # (sharded, not exact: every rank makes the uniform attempt, api.hip:3062, and a group that
-            # does not stand on every rank falls back; exact: no attempt and no aligned group, :2997)
+            # (sharded, not exact: every rank makes the uniform attempt, api.hip: SgCall::uniform_try, and a group that
+            # does not stand on every rank falls back; exact: no attempt and no aligned group, api.hip: SgCall::plan)
             p = check(mctx, lg, agg, False, 60, AVG, exact)
             if exact:
                 expect(p, 0, UNI | LS | GD | AG | AR | REDONE, q)
